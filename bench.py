@@ -14,10 +14,14 @@ collective per batch, issued from the decode lanes, hands work between the lanes
 stream and serialised the two-lane pipeline in a one-GPU rehearsal:
 profiles/r01_gather_topology.txt.)
 
-Rank 0 prints ONE JSON line.  `roofline` is priced on the dominant kernel (the ViT fc1 GEMM,
-`vcap_gemm_kernel<bf16,bf16,1>`), timed live with HIP events around each of its launches in
-the timed region (vcap_probe_*).  `cpu_baseline` times the CPU oracle (fp32 torch restatement
-of the reference path, oracle/vcap_oracle.py) on a bounded sample on the host cores (N=1 only).
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up,
+warm-up, the timed steps, `--dump-outputs` if given, and the line.  Every other leg (host-pinned
+latency, strict_batch, token_exact, the --batch-sizes sweep, the fp32 parity report, the decode step
+alone, the CPU baseline and the oracle agreement) runs only with `--full`.  `roofline` is priced
+on the dominant kernel (the ViT fc1 GEMM, `vcap_gemm_kernel<bf16,bf16,1>`), timed live with HIP
+events around each of its launches in the timed region (vcap_probe_*).  `cpu_baseline` (--full)
+times the CPU oracle (fp32 torch restatement of the reference path, oracle/vcap_oracle.py) on a
+bounded sample on the host cores (N=1 only).
 """
 from __future__ import annotations
 
@@ -121,10 +125,25 @@ def parse():
                     help="per-iteration CSV of the timed batches (the reference's export_iteration_csv columns); "
                          "with --batch-sizes: the batch-size comparison CSV (export_bs_comparison_csv)")
     ap.add_argument("--export-json", default="", help="summary JSON (the reference's export_summary_json payload)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32): token_ids = the last timed batch's [world * B, max_new] ids")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: --host-e2e, --strict-steps, --token-exact-steps, "
+                         "--batch-sizes, the parity report, the decode step alone and --cpu-baseline-s (+ oracle "
+                         "agreement); without it those options are ignored and their fields are null")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher check only: every rank joins the process group (gloo), barriers, gathers its "
                          "rank and exits; no GPU work (tests/test_cpu_bench_launch.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.batch_sizes and not args.full:
+        ap.error("--batch-sizes is a --full leg: add --full")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        args.host_e2e, args.cpu_baseline_s, args.strict_steps, args.token_exact_steps = 0, 0.0, 0, 0
+        args.parity = args.decode_alone = False
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -570,6 +589,19 @@ def export(args, out, B, lat, vit_ms, dec_ms, ids_all, dec_alone, sweep_rows, eo
                                                       "iterations": rows, "bench_line": out})
 
 
+def dump_outputs(out_dir, last, gathered, world, steps, rank):
+    """--dump-outputs: the ids the last timed step handed its caller (pipe.result of the last timed
+    submission; for N ranks every rank's last timed batch out of the end-of-run gather, rank-major),
+    as float32 (ids < 2^24 are exact)."""
+    import numpy as np
+    import torch
+    if gathered is not None:
+        last = torch.cat([gathered[r * steps + steps - 1] for r in range(world)])
+    if rank == 0:
+        Path(out_dir).mkdir(parents=True, exist_ok=True)
+        np.save(Path(out_dir) / "token_ids.npy", last.cpu().numpy().astype(np.float32))
+
+
 def workload_tag(args, world):
     if args.precision == "fp8":
         return "configs[4]-shaped, MXFP8 ViT GEMMs"
@@ -707,6 +739,10 @@ def main():
     for site, launches in probes.items():
         if len(launches) != expected:
             raise RuntimeError(f"probe {site}: {len(launches)} launches in the timed region, expected {expected}")
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe.result(pipe.last_slot), gathered if world > 1 else None,
+                     world, args.steps, rank)
 
     # SURVEY 8(d) latency: a host-pinned [B,T,3,H,W] fp32 tensor -> H2D -> encode -> decode ->
     # token ids on the host, one batch at a time (outside the timed throughput region)

@@ -7,6 +7,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 from vcap import report
@@ -25,7 +26,14 @@ def _bench(args):
 
 def test_iteration_exports(tmp_path):
     c, j = tmp_path / "it.csv", tmp_path / "s.json"
-    line = _bench(["--steps", "6", "--export-csv", str(c), "--export-json", str(j)])
+    line = _bench(["--steps", "6", "--export-csv", str(c), "--export-json", str(j),
+                   "--dump-ids", str(tmp_path / "ids.npy"), "--dump-outputs", str(tmp_path / "out")])
+    # a plain run (no --full): the headline only, and --dump-outputs = the last timed batch's ids
+    assert line["steps"] == 6 and abs(line["ms_per_step"] * line["value"] - 8e3) < 1e-6 * 8e3
+    assert all(line[k] is None for k in ("strict_batch", "token_exact", "batch_sweep", "parity", "decode_roofline",
+                                         "cpu_baseline")) and "host_e2e" not in line
+    ids, out = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "out" / "token_ids.npy")
+    assert ids.shape == (6, 8, 24) and out.dtype == np.float32 and np.array_equal(out, ids[-1])
     with open(c) as fh:
         rows = list(csv.DictReader(fh))
     assert list(rows[0].keys()) == report.ITERATION_FIELDS and len(rows) == 6
@@ -40,7 +48,7 @@ def test_iteration_exports(tmp_path):
 
 def test_batch_size_comparison_exports(tmp_path):
     c, j = tmp_path / "cmp.csv", tmp_path / "cmp.json"
-    _bench(["--steps", "4", "--batch-sizes", "2,8", "--sweep-steps", "4", "--export-csv", str(c),
+    _bench(["--full", "--steps", "4", "--batch-sizes", "2,8", "--sweep-steps", "4", "--export-csv", str(c),
             "--export-json", str(j)])
     with open(c) as fh:
         rows = list(csv.DictReader(fh))

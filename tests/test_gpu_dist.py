@@ -88,7 +88,7 @@ def test_bench_two_ranks_gloo(tmp_path, device, launcher):
     run = ([sys.executable] if launcher == "self" else
            [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
             "--master-addr=127.0.0.1", f"--master-port={_free_port()}"])
-    cmd = run + [str(HERE.parent / "bench.py"), "--gpus", "2",
+    cmd = run + [str(HERE.parent / "bench.py"), "--gpus", "2", "--full",
                  "--steps", str(steps), "--warmup", "2", "--cpu-baseline-s", "0", "--no-parity", "--no-decode-alone",
                  "--host-e2e", "0", "--strict-steps", "2", "--dump-ids", str(dump)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=200)

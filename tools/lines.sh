@@ -4,12 +4,12 @@
 # usage: tools/lines.sh <outdir>
 out=${1:-gpurun_out/lines}
 mkdir -p $out
-timeout -k 10 600 python -u bench.py --precision fp8 --batch 16 --steps 20 --warmup 5 > $out/bench_fp8.json 2> $out/bench_fp8.err
+timeout -k 10 600 python -u bench.py --full --precision fp8 --batch 16 --steps 20 --warmup 5 > $out/bench_fp8.json 2> $out/bench_fp8.err
 rc=$?; echo "fp8 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 C3="--vit vit_large_patch14_224 --gpt2 gpt2-medium --frames 32 --batch 4 --beams 4 --max-new 40 --steps 24 --warmup 3"
-timeout -k 10 700 python -u bench.py $C3 > $out/bench_c3_bf16.json 2> $out/bench_c3_bf16.err
+timeout -k 10 700 python -u bench.py --full $C3 > $out/bench_c3_bf16.json 2> $out/bench_c3_bf16.err
 rc=$?; echo "c3 bf16 rc=$rc"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 900 python -u bench.py $C3 --precision fp32 > $out/bench_c3_fp32.json 2> $out/bench_c3_fp32.err
+timeout -k 10 900 python -u bench.py --full $C3 --precision fp32 > $out/bench_c3_fp32.json 2> $out/bench_c3_fp32.err
 rc=$?; echo "c3 fp32 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 python3 - $out <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeou
 rc=$?; echo "gpu suite rc=$rc"; tail -4 $out/gpu_tests.txt; ok $rc || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $out/smoke.txt; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 bash tools/prof_default.sh $out/prof > $out/prof.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
