@@ -38,15 +38,22 @@
 extern "C" {
 #endif
 
-#define VCAP_ABI_VERSION 15
+#define VCAP_ABI_VERSION 16
 
 /* VCAP_DT_MXFP8: OCP e4m3fn elements + one E8M0 scale per 32 consecutive K elements of a row
  * (the gfx950 block-scaled MFMA format; BASELINE configs[4]).  Scale arrays use the GEMM's
  * staging order: per (128-wide K-tile, group of 256 rows) one 1 KiB block laid out
  * [k-block 0..3][row % 16][row / 16] - byte offset
  *   ((k/128 * ceil(rows/256) + row/256) * 4 + (k%128)/32) * 256 + (row%16) * 16 + (row%256)/16,
- * size vcap_mx_scale_bytes(rows, K).  Element value = e4m3 * 2^(scale - 127). */
-enum { VCAP_DT_F32 = 0, VCAP_DT_BF16 = 1, VCAP_DT_MXFP8 = 2 };
+ * size vcap_mx_scale_bytes(rows, K).  Element value = e4m3 * 2^(scale - 127).
+ * VCAP_DT_F16: IEEE binary16 (torch.float16), the dtype of the reference's ViT autocast
+ * (src/models/video_encoder.py:261-264).  A ViT operand format only: vcap_vit_desc.dtype, vcap_gemm,
+ * vcap_linear_bias, vcap_layernorm, vcap_vit_attention, vcap_vit_qkv_attention_dt and
+ * vcap_vit_pool_temporal take it; the decoder (vcap_gpt2_*, vcap_rows_pack*, vcap_decode_attention)
+ * and the MXFP8 entry points refuse it.  With F16 operands a GEMM rounds where autocast does: the
+ * accumulator + bias to fp16 before an f32 residual / positional add, and the GELU's input and
+ * output to fp16; conversions round to nearest even, overflow to +-inf, subnormals kept. */
+enum { VCAP_DT_F32 = 0, VCAP_DT_BF16 = 1, VCAP_DT_MXFP8 = 2, VCAP_DT_F16 = 3 };
 enum { VCAP_E_ARG = -1000, VCAP_E_WORKSPACE = -1001, VCAP_E_UNSUPPORTED = -1002 };
 
 typedef struct vcap_vit_layer {
@@ -62,7 +69,8 @@ typedef struct vcap_vit_layer {
 } vcap_vit_layer;
 
 typedef struct vcap_vit_desc {
-  int dtype;                 /* operand dtype of the block GEMMs (VCAP_DT_*; MXFP8: QKV / attn-proj /
+  int dtype;                 /* operand dtype of the block GEMMs (VCAP_DT_*; F16: weights fp16, workspace
+                                as BF16's, autocast's rounding points; MXFP8: QKV / attn-proj /
                                 fc1 / fc2 in MXFP8 with LayerNorm, attention and GELU emitting MXFP8
                                 operands; patch-embed and the QK^T / PV products in bf16) */
   int dim, depth, heads, patch, image, mlp, video_dim;
@@ -153,6 +161,17 @@ int vcap_linear_bias(int dtype, const void* x, const void* w, const float* b, vo
 int vcap_gemm(int in_dtype, int out_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
               int64_t ldc, int M, int N, int K, const float* bias, int act, const float* res, int64_t ldr,
               int res_mode, int G, int Gs, int goff, int roff, void* stream);
+/* The in-place residual GEMM of the encoder's class-token-only last block, at the op level:
+ *   C[orow(m)][n] += sum_k A[m][k] W[n][k] + bias[n],   orow(m) = G ? (m / G) * Gs + m % G : m
+ * with BF16 or F16 operands, f32 C, and a caller workspace (>= 8 * M * N * 4 bytes, 16-byte aligned) for
+ * deterministic split-K partials: where the dispatcher runs the 128x128 kernel (few tiles, gemm policy 0
+ * or 1) K is split over the largest c <= 8 dividing the K-tile count with >= 3 K-tiles per split, the
+ * partial slabs are summed in split order by a second kernel, and - F16 - the sum + bias is rounded to
+ * fp16 there, before the add.  *splits_out (optional) receives c (1: not split).  This is the path
+ * vcap_vit_encode takes for attn-proj / fc2 of its last block. */
+int vcap_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc,
+                     int M, int N, int K, const float* bias, int G, int Gs, void* workspace, size_t ws_bytes,
+                     int* splits_out, void* stream);
 int vcap_layernorm(int out_dtype, const float* x, int64_t ldx, void* y, int64_t ldy, const float* gamma,
                    const float* beta, int rows, int dim, float eps, void* stream);
 int vcap_vit_attention(int dtype, const void* qkv, void* out, int frames, int tokens, int heads, void* stream);
@@ -165,6 +184,10 @@ int vcap_vit_attention(int dtype, const void* qkv, void* out, int frames, int to
  * (src/models/video_encoder.py:112-121).  VCAP_E_UNSUPPORTED outside that shape. */
 int vcap_vit_qkv_attention(const void* xn, const void* wqkv, const float* bqkv, void* out, int frames, int tokens,
                            int heads, int cls_only, void* stream);
+/* The same with the 2-byte element type chosen: dtype VCAP_DT_BF16 (= vcap_vit_qkv_attention) or
+ * VCAP_DT_F16 (xn, wqkv and out fp16; bit-identical to the F16 vcap_gemm + vcap_vit_attention pair). */
+int vcap_vit_qkv_attention_dt(int dtype, const void* xn, const void* wqkv, const float* bqkv, void* out, int frames,
+                              int tokens, int heads, int cls_only, void* stream);
 
 /* ---- frame preprocessing (core/preprocessing/frame_loader.py:34-45: torchvision Resize((S, S)) on
  *      PIL images -> ToTensor -> Normalize): decoded RGB frames uint8 [n, in_h, in_w, 3] (device)

@@ -48,8 +48,9 @@ def parse(argv=None):
     ap.add_argument("--num_frames", type=int, default=16)
     ap.add_argument("--vit_name", default="vit_base_patch16_224")
     ap.add_argument("--gpt2_name", default="gpt2")
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8"],
-                    help="ViT arithmetic: bf16 = the reference's half-precision autocast; fp32 = the parity mode; "
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32", "fp8"],
+                    help="ViT arithmetic: bf16 = the throughput default; fp16 = the reference's autocast dtype; "
+                         "fp32 = the parity mode; "
                          "fp8 = MXFP8 ViT GEMMs")
     ap.add_argument("--decoder_precision", default="auto", choices=["auto", "fp32", "bf16"],
                     help="GPT-2 decoder arithmetic: auto = fp32, the reference's (token-exact captions); "

@@ -1,8 +1,8 @@
-"""Instruction counts of the bench's ViT attention kernel (vcap_vit_attention_bf16_kernel<14,13,8,false>,
+"""Instruction counts of the bench's ViT attention kernel (vcap_vit_attention_bf16_kernel<14,13,8,false,bf16>,
 ViT-B/16: 197 tokens -> 13 query tiles and 14 key tiles of 16) from its gfx950 assembly, and the issue- and
 traffic-bound ceilings on its MFMA utilisation that follow.  Runs on the CPU (hipcc -S).
 
-usage: python tools/attn_isa_counts.py [kernel-suffix]   (default ILi14ELi13ELi8ELb0E)"""
+usage: python tools/attn_isa_counts.py [kernel-suffix]   (default ILi14ELi13ELi8ELb0EtE: bf16; the fp16 twin is ILi14ELi13ELi8ELb0EDF16_E)"""
 import collections
 import re
 import subprocess
@@ -12,7 +12,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "video-caption-algorithm_amd" / "csrc"
-suffix = sys.argv[1] if len(sys.argv) > 1 else "ILi14ELi13ELi8ELb0E"
+suffix = sys.argv[1] if len(sys.argv) > 1 else "ILi14ELi13ELi8ELb0EtE"
 
 with tempfile.TemporaryDirectory() as td:
     asm = Path(td) / "attn.s"

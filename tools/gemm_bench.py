@@ -1,6 +1,9 @@
 """ViT GEMM shapes (B=8 videos x 16 frames x 197 tokens = 25216 rows, ViT-B/16) through vcap_gemm
 with the 128x128 kernel (policy 1) and the 256x256 8-phase kernel (policy 2), interleaved rounds in
-one process on random bf16 operands.  Prints TFLOP/s per shape and policy (median of rounds)."""
+one process on random bf16 operands.  Prints TFLOP/s per shape and policy (median of rounds).
+DTYPES=bf16,fp16 (environment; default bf16) times the listed 2-byte operand types side by side: every
+round runs each shape in each dtype, so the two share the clocks and the drift of one run."""
+import os
 import statistics
 import sys
 from pathlib import Path
@@ -28,47 +31,54 @@ shapes = {  # name: (N, K, out f32?, act, residual)
     "fc1": (3072, 768, False, 1, False),
     "fc2": (768, 3072, True, 0, True),
 }
+DT = {"bf16": (N.DT_BF16, torch.bfloat16), "fp16": (N.DT_F16, torch.float16)}
+DTYPES = [d for d in os.environ.get("DTYPES", "bf16").split(",") if d]
 bufs = {}
-for name, (n, k, f32, act, res) in shapes.items():
-    A = rnd(M, k)
-    W = rnd(n, k, scale=0.05)
-    b = rnd(n, scale=0.1, dtype=torch.float32)
-    C = torch.zeros(M, n, device=dev, dtype=torch.float32 if f32 else torch.bfloat16)
-    bufs[name] = (A, W, b, C)
+for dname in DTYPES:
+    for name, (n, k, f32, act, res) in shapes.items():
+        A = rnd(M, k, dtype=DT[dname][1])
+        W = rnd(n, k, scale=0.05, dtype=DT[dname][1])
+        b = rnd(n, scale=0.1, dtype=torch.float32)
+        C = torch.zeros(M, n, device=dev, dtype=torch.float32 if f32 else DT[dname][1])
+        bufs[(dname, name)] = (A, W, b, C)
 
 
-def run(name, reps):
+def run(dname, name, reps):
     n, k, f32, act, res = shapes[name]
-    A, W, b, C = bufs[name]
-    odt = N.DT_F32 if f32 else N.DT_BF16
+    A, W, b, C = bufs[(dname, name)]
+    idt = DT[dname][0]
+    odt = N.DT_F32 if f32 else idt
     for _ in range(reps):
-        N.check(lib.vcap_gemm(N.DT_BF16, odt, A.data_ptr(), k, W.data_ptr(), k, C.data_ptr(), n, M, n, k,
+        N.check(lib.vcap_gemm(idt, odt, A.data_ptr(), k, W.data_ptr(), k, C.data_ptr(), n, M, n, k,
                               b.data_ptr(), act, C.data_ptr() if res else None, n if res else 0, 1 if res else 0,
                               0, 0, 0, 0, s), name)
 
 
 POL = (1, 2, 0)
-times = {(nm, p): [] for nm in shapes for p in POL}
+times = {(d, nm, p): [] for d in DTYPES for nm in shapes for p in POL}
 for p in POL:
     lib.vcap_set_gemm_policy(p)
     for nm in shapes:
-        run(nm, 3)
+        for d in DTYPES:
+            run(d, nm, 3)
 torch.cuda.synchronize()
 for rnd_i in range(5):
     for p in POL:
         lib.vcap_set_gemm_policy(p)
         for nm in shapes:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            run(nm, 10)
-            e1.record()
-            e1.synchronize()
-            times[(nm, p)].append(e0.elapsed_time(e1) / 10)
+            for d in DTYPES:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run(d, nm, 10)
+                e1.record()
+                e1.synchronize()
+                times[(d, nm, p)].append(e0.elapsed_time(e1) / 10)
 lib.vcap_set_gemm_policy(0)
 for nm, (n, k, *_) in shapes.items():
     fl = 2.0 * M * n * k
-    row = [f"{nm:5s} M={M} N={n} K={k}:"]
-    for p in POL:
-        ms = statistics.median(times[(nm, p)])
-        row.append(f"{['auto', 'tile128', 'tile256'][p]} {ms * 1e3:7.1f} us {fl / ms / 1e9:7.1f} TF")
-    print("  ".join(row), flush=True)
+    for d in DTYPES:
+        row = [f"{nm:5s} {d} M={M} N={n} K={k}:"]
+        for p in POL:
+            ms = statistics.median(times[(d, nm, p)])
+            row.append(f"{['auto', 'tile128', 'tile256'][p]} {ms * 1e3:7.1f} us {fl / ms / 1e9:7.1f} TF")
+        print("  ".join(row), flush=True)

@@ -11,7 +11,8 @@
 // global_load_lds_dwordx4 (1 KiB per wave instruction, lane-linear LDS image); the
 // st_8x16B XOR swizzle (chunk ^ (row & 7)) is applied on the global SOURCE address and on
 // the ds_read address, making the ds_read_b128 fragment reads conflict-free.
-// bf16 uses mfma_f32_16x16x32_bf16; the fp32 parity mode uses mfma_f32_16x16x4f32 with the
+// bf16 / f16 use mfma_f32_16x16x32_bf16 / _f16 (f16: the reference's autocast dtype, rounded where
+// autocast rounds: Autocast<T> in vcap_common.h); the fp32 parity mode uses mfma_f32_16x16x4f32 with the
 // SAME byte layout (one 16-byte chunk = 4 f32 = one group of four 16x16x4 MFMAs).
 #include "vcap_common.h"
 #include "vcap_kernels.h"
@@ -156,17 +157,28 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + bias[e];
+      // f16 operands: the Linear's output is fp16 under autocast (the split-K sum rounds in its reduce;
+      // a plain 16-bit store rounds by itself, and rounding is idempotent)
+      if constexpr (Autocast<TIn>::kRound && !(EPI == 0 && sizeof(TOut) == 2)) {
+        if (!split)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = Autocast<TIn>::rnd(v[e]);
+      }
       if (split) {  // raw partial sums (N % 4 == 0: dispatcher)
         *reinterpret_cast<f32x4*>(epi.splitk_ws + ((long)blockIdx.y * M + m) * N + nb) = (f32x4){v[0], v[1], v[2], v[3]};
         continue;
       }
+      // The GELU's output is rounded by the 16-bit store itself (the packed f32x2 conversion: the
+      // product is rounded to f32, then to f16, in both GEMM kernels; a scalar conversion here could be
+      // contracted with the GELU's last multiply into one v_fma_mixlo_f16, which rounds once and would
+      // differ from the 256x256 kernel at f16 ties).  Only an f32 output needs the explicit rounding.
       if constexpr (EPI == 1) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
       } else if constexpr (EPI == 3) {
         if (epi.act == 1)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
+          for (int e = 0; e < 4; ++e) v[e] = sizeof(TOut) == 4 ? Autocast<TIn>::rnd(gelu_tanh(v[e])) : gelu_tanh(v[e]);
       }
       const float* rr = nullptr;
       if constexpr (EPI == 2) rr = epi.res + orow * epi.ldr + nb;
@@ -183,7 +195,8 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
           v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
         }
         if constexpr (sizeof(TOut) == 2) {
-          *reinterpret_cast<u32x2*>(C + orow * ldc + nb) = (u32x2){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+          *reinterpret_cast<u32x2*>(C + orow * ldc + nb) =
+              (u32x2){Pack2<TOut>::pack(v[0], v[1]), Pack2<TOut>::pack(v[2], v[3])};
         } else {
           *reinterpret_cast<f32x4*>(C + orow * ldc + nb) = (f32x4){v[0], v[1], v[2], v[3]};
         }
@@ -199,7 +212,9 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
 }
 
 // C[orow(m)][n] = (sum over splits s = 0.. of ws[s][m][n] + bias[n]) + C[orow(m)][n]: the split-K
-// partials of an in-place residual GEMM, summed in a fixed order.
+// partials of an in-place residual GEMM, summed in a fixed order.  R16 (f16 operands): the sum + bias is
+// rounded to fp16 before the residual add, where the unsplit epilogue rounds it.
+template <bool R16>
 __global__ __launch_bounds__(256) void vcap_splitk_reduce_kernel(const float* __restrict__ ws, int splits, float* C,
                                                                  long ldc, int M, int N, GemmEpi epi) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;  // f32x4 index
@@ -209,10 +224,15 @@ __global__ __launch_bounds__(256) void vcap_splitk_reduce_kernel(const float* __
   f32x4 v = *reinterpret_cast<const f32x4*>(ws + (long)m * N + n);
   for (int sp = 1; sp < splits; ++sp) v += *reinterpret_cast<const f32x4*>(ws + ((long)sp * M + m) * N + n);
   if (epi.bias) v += *reinterpret_cast<const f32x4*>(epi.bias + n);
+  if constexpr (R16) v = Autocast<f16_t>::rnd4(v);
   const long orow = epi.G ? (long)(m / epi.G) * epi.Gs + epi.goff + (m % epi.G) : (long)m;
   float* c = C + orow * ldc + n;
   *reinterpret_cast<f32x4*>(c) = v + *reinterpret_cast<const f32x4*>(c);
 }
+
+// K splits of the latest 128x128 launch issued by this thread (1 = unsplit): vcap_gemm_splitk reports it
+static thread_local int g_last_splits = 1;
+int vcap_gemm_last_splits() { return g_last_splits; }
 
 template <typename TIn, typename TOut, int EPI>
 static hipError_t launch_gemm_epi(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N,
@@ -220,7 +240,7 @@ static hipError_t launch_gemm_epi(const void* A, long lda, const void* W, long l
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   // Few tiles (the CLS-only last block: M = B*T rows) leave most CUs idle through a long K
   // loop: split K over several workgroups per tile when C is f32 and already holds the
-  // residual (attn-proj / fc2 in place) and the caller gave a partials workspace (bf16 operands
+  // residual (attn-proj / fc2 in place) and the caller gave a partials workspace (bf16 / f16 operands
   // only: the fp32 parity mode keeps one summation chain).  The split count depends on K alone
   // (the largest divisor c <= 8 of the K-tile count leaving >= 3 K-tiles per workgroup), never on
   // M or the stream's CU mask, so a row sums the same way whichever batch it is encoded in and a
@@ -243,12 +263,13 @@ static hipError_t launch_gemm_epi(const void* A, long lda, const void* W, long l
     if (in_place && c > 1 && (size_t)c * M * N * sizeof(float) <= epi.splitk_bytes)
       splits = c;
   }
+  g_last_splits = splits;
   hipLaunchKernelGGL((vcap_gemm_kernel<TIn, TOut, EPI>), dim3(tiles, splits), dim3(256), 0, s, (const TIn*)A, lda,
                      (const TIn*)W, ldw, (TOut*)C, ldc, M, N, K, epi);
   if (splits > 1) {
     if (hipError_t e = hipGetLastError()) return e;
     const long nvec = (long)M * (N / 4);
-    hipLaunchKernelGGL(vcap_splitk_reduce_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(vcap_splitk_reduce_kernel<Autocast<TIn>::kRound>, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s,
                        (const float*)epi.splitk_ws, splits, (float*)C, ldc, M, N, epi);
   }
   return hipGetLastError();
@@ -269,6 +290,22 @@ static hipError_t launch_gemm(const void* A, long lda, const void* W, long ldw, 
       return launch_gemm_epi<TIn, TOut, 2>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
   }
   return launch_gemm_epi<TIn, TOut, 3>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+}
+
+// the 128x128 kernel of an (operand, output) dtype pair: a 2-byte operand type writes itself or f32
+static hipError_t launch_gemm_dt(int in_dt, int out_dt, const void* A, long lda, const void* W, long ldw, void* C,
+                                 long ldc, int M, int N, int K, const GemmEpi& epi, hipStream_t s) {
+  if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_BF16)
+    return launch_gemm<bf16_t, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_F32)
+    return launch_gemm<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_F16 && out_dt == VCAP_DT_F16)
+    return launch_gemm<f16_t, f16_t>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_F16 && out_dt == VCAP_DT_F32)
+    return launch_gemm<f16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_F32 && out_dt == VCAP_DT_F32)
+    return launch_gemm<float, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  return hipErrorInvalidValue;
 }
 
 static int g_gemm_policy = 0;  // 0 auto, 1 always the 128x128 kernel, 2 the 256x256 kernel where it applies
@@ -295,6 +332,7 @@ int vcap_stream_cus(hipStream_t s) {
 // in_dt: operand dtype; out_dt: C dtype (the residual stream is f32)
 hipError_t vcap_gemm_dispatch(int in_dt, int out_dt, const void* A, long lda, const void* W, long ldw, void* C,
                               long ldc, int M, int N, int K, const GemmEpi& epi, hipStream_t s) {
+  g_last_splits = 1;  // the 256x256 kernel never splits
   if (in_dt == VCAP_DT_MXFP8) {  // block-scaled fp8: the 256x256 kernel only
     if (!vcap_gemm256_ok(in_dt, out_dt, lda, ldw, ldc, M, N, K, epi)) return hipErrorInvalidValue;
     return vcap_gemm256_dispatch(in_dt, out_dt, A, lda, W, ldw, C, ldc, M, N, K, epi, s);
@@ -315,27 +353,18 @@ hipError_t vcap_gemm_dispatch(int in_dt, int out_dt, const void* A, long lda, co
       if (plain && rem > 0 && rem * 4 < ncu && m_full > 0 && m_full < M) {
         if (hipError_t e = vcap_gemm256_dispatch(in_dt, out_dt, A, lda, W, ldw, C, ldc, m_full, N, K, epi, s))
           return e;
-        const size_t ein = in_dt == VCAP_DT_BF16 ? 2 : 4, eout = out_dt == VCAP_DT_BF16 ? 2 : 4;
+        const size_t ein = vcap_dt_size(in_dt), eout = vcap_dt_size(out_dt);
         GemmEpi e2 = epi;
         if (epi.res) e2.res = epi.res + (long)m_full * epi.ldr;
         const void* A2 = (const char*)A + (size_t)m_full * lda * ein;
         void* C2 = (char*)C + (size_t)m_full * ldc * eout;
-        if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_BF16)
-          return launch_gemm<bf16_t, bf16_t>(A2, lda, W, ldw, C2, ldc, M - m_full, N, K, e2, s);
-        if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_F32)
-          return launch_gemm<bf16_t, float>(A2, lda, W, ldw, C2, ldc, M - m_full, N, K, e2, s);
-        return launch_gemm<float, float>(A2, lda, W, ldw, C2, ldc, M - m_full, N, K, e2, s);
+        return launch_gemm_dt(in_dt, out_dt, A2, lda, W, ldw, C2, ldc, M - m_full, N, K, e2, s);
       }
       return vcap_gemm256_dispatch(in_dt, out_dt, A, lda, W, ldw, C, ldc, M, N, K, epi, s);
     }
   }
-  if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_BF16)
-    return launch_gemm<bf16_t, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
-  if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_F32)
-    return launch_gemm<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
-  if (in_dt == VCAP_DT_F32 && out_dt == VCAP_DT_F32)
-    return launch_gemm<float, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
-  return hipErrorInvalidValue;
+  return launch_gemm_dt(in_dt, out_dt, A, lda, W, ldw, C, ldc, M, N, K, epi, s);
 }
 
-int vcap_gemm_k_align(int in_dt) { return in_dt == VCAP_DT_MXFP8 ? 256 : in_dt == VCAP_DT_BF16 ? 64 : 32; }
+// one 128-byte K-tile row (two for the MXFP8 kernel's paired K-tiles)
+int vcap_gemm_k_align(int in_dt) { return in_dt == VCAP_DT_MXFP8 ? 256 : vcap_dt_is16(in_dt) ? 64 : 32; }

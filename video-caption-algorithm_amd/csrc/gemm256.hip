@@ -88,6 +88,13 @@ VCAP_DEV void out_store(V* p, const V& v) {
   else __builtin_nontemporal_store(v, p);
 }
 
+// the 16-byte-store branch of the epilogue is guarded at run time, so it is compiled for every TOut
+template <typename TOut>
+VCAP_DEV uint32_t pack_out2(float lo, float hi) {
+  if constexpr (sizeof(TOut) == 2) return Pack2<TOut>::pack(lo, hi);
+  else return 0u;
+}
+
 VCAP_DEV void lds_fence() { asm volatile("" ::: "memory"); }
 
 }  // namespace
@@ -187,9 +194,11 @@ VCAP_DEV void epilogue256(const f32x4 (&acc)[2][2][4][2], int m0, int n0, int wr
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             f32x4 v = acc[qm][qn][i][j] + bias[j];
-            if constexpr (EPI == 1) v = gelu_tanh4(v);
-            p[j][0] = pack_bf2(v.x, v.y);
-            p[j][1] = pack_bf2(v.z, v.w);
+            // f16 operands: autocast's Linear returns fp16, so the GELU sees the rounded value (the
+            // store's own rounding is the Linear's when there is no activation)
+            if constexpr (EPI == 1) v = gelu_tanh4(Autocast<TIn>::rnd4(v));
+            p[j][0] = pack_out2<TOut>(v.x, v.y);
+            p[j][1] = pack_out2<TOut>(v.z, v.w);
           }
           const uint32_t r0 = (uint32_t)xor16_i((int)(odd ? p[0][0] : p[1][0]));
           const uint32_t r1 = (uint32_t)xor16_i((int)(odd ? p[0][1] : p[1][1]));
@@ -229,7 +238,7 @@ VCAP_DEV void epilogue256(const f32x4 (&acc)[2][2][4][2], int m0, int n0, int wr
         for (int j = 0; j < 2; ++j) {
           const int m = m0 + wr * 128 + qm * 64 + i * 16 + fr;
           const int n = n0 + wc * 64 + qn * 32 + j * 16 + fg * 4;
-          const f32x4 v = acc[qm][qn][i][j] + bias[qn][j] + r[i][j];
+          const f32x4 v = Autocast<TIn>::rnd4(acc[qm][qn][i][j] + bias[qn][j]) + r[i][j];
           if (m < M && n < N) out_store(reinterpret_cast<f32x4*>(C + (long)m * ldc + n), v);
         }
     };
@@ -257,7 +266,10 @@ VCAP_DEV void epilogue256(const f32x4 (&acc)[2][2][4][2], int m0, int n0, int wr
           const int m = m0 + wr * 128 + qm * 64 + i * 16 + fr;
           if (m >= M) continue;
           f32x4 v = acc[qm][qn][i][j] + bias;
+          if constexpr (!(EPI == 0 && sizeof(TOut) == 2)) v = Autocast<TIn>::rnd4(v);  // (a 16-bit store rounds itself)
           long orow = m;
+          // (the GELU's output is rounded by the packed 16-bit store, as in the 16-byte branch and in the
+          // 128x128 kernel; only an f32 output rounds it explicitly)
           if constexpr (EPI == 1) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
@@ -266,14 +278,15 @@ VCAP_DEV void epilogue256(const f32x4 (&acc)[2][2][4][2], int m0, int n0, int wr
           } else if constexpr (EPI == 3) {
             if (epi.act == 1)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
+              for (int e = 0; e < 4; ++e) v[e] = sizeof(TOut) == 4 ? Autocast<TIn>::rnd(gelu_tanh(v[e])) : gelu_tanh(v[e]);
             orow = epi.G ? (long)(m / epi.G) * epi.Gs + epi.goff + (m % epi.G) : (long)m;
             if (epi.res_mode == 1) v += *reinterpret_cast<const f32x4*>(epi.res + orow * epi.ldr + n);
             else if (epi.res_mode == 2)
               v += *reinterpret_cast<const f32x4*>(epi.res + (long)((m % epi.G) + epi.roff) * epi.ldr + n);
           }
           if constexpr (sizeof(TOut) == 2) {
-            out_store(reinterpret_cast<u32x2*>(C + orow * ldc + n), (u32x2){pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)});
+            out_store(reinterpret_cast<u32x2*>(C + orow * ldc + n),
+                      (u32x2){Pack2<TOut>::pack(v.x, v.y), Pack2<TOut>::pack(v.z, v.w)});
           } else {
             out_store(reinterpret_cast<f32x4*>(C + orow * ldc + n), v);
           }
@@ -580,9 +593,10 @@ static hipError_t launch256(const void* A, long lda, const void* W, long ldw, vo
 // Shapes this kernel takes: K a multiple of two K-tiles, N and the strides in whole 16-byte
 // vectors for the epilogue, 16-byte aligned bias / residual rows.
 bool vcap_gemm256_ok(int in_dt, int out_dt, long lda, long ldw, long ldc, int M, int N, int K, const GemmEpi& epi) {
-  const int bk = in_dt == VCAP_DT_MXFP8 ? 128 : in_dt == VCAP_DT_BF16 ? 64 : 32;
+  if (!vcap_dt_size(in_dt) || !vcap_dt_size(out_dt)) return false;
+  const int bk = 128 / (int)vcap_dt_size(in_dt);  // one 128-byte K-tile row
   if (K % (2 * bk) != 0 || N % 16 != 0 || M <= 0) return false;
-  const int ein = in_dt == VCAP_DT_MXFP8 ? 16 : in_dt == VCAP_DT_BF16 ? 8 : 4;
+  const int ein = 16 / (int)vcap_dt_size(in_dt);  // elements per 16-byte vector
   if (in_dt == VCAP_DT_MXFP8 && (!epi.a_scale || !epi.w_scale)) return false;
   if (out_dt == VCAP_DT_MXFP8 && (in_dt != VCAP_DT_MXFP8 || N % 128 || ldc % 16 || epi.act != 1 || !epi.bias ||
                                   !epi.c_scale || epi.G || epi.res_mode))
@@ -601,6 +615,10 @@ hipError_t vcap_gemm256_dispatch(int in_dt, int out_dt, const void* A, long lda,
     return launch256<bf16_t, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
   if (in_dt == VCAP_DT_BF16 && out_dt == VCAP_DT_F32)
     return launch256<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_F16 && out_dt == VCAP_DT_F16)
+    return launch256<f16_t, f16_t>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
+  if (in_dt == VCAP_DT_F16 && out_dt == VCAP_DT_F32)
+    return launch256<f16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
   if (in_dt == VCAP_DT_F32 && out_dt == VCAP_DT_F32)
     return launch256<float, float>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
   if (in_dt == VCAP_DT_MXFP8 && out_dt == VCAP_DT_BF16)

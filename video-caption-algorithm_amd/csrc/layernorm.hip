@@ -1,4 +1,4 @@
-// Row LayerNorm: f32 residual stream -> T (bf16 MFMA operand, or f32 in parity mode).
+// Row LayerNorm: f32 residual stream -> T (bf16 / f16 MFMA operand, or f32 in parity mode).
 // ViT norm1/norm2 (eps 1e-6, timm Block, src/models/video_encoder.py:168-170) and the
 // engine's prefix layer_norm without affine (core/engine.py:47-48, eps 1e-5).
 // One wave per row, two-pass mean/variance in fp32 registers, float4 loads.
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void vcap_layernorm_kernel(const float* __rest
           o = o * g + b;
         }
         if constexpr (sizeof(TOut) == 2) {
-          *reinterpret_cast<u32x2*>(yr + c) = (u32x2){pack_bf2(o.x, o.y), pack_bf2(o.z, o.w)};
+          *reinterpret_cast<u32x2*>(yr + c) = (u32x2){Pack2<TOut>::pack(o.x, o.y), Pack2<TOut>::pack(o.z, o.w)};
         } else {
           *reinterpret_cast<f32x4*>(yr + c) = o;
         }
@@ -160,7 +160,14 @@ hipError_t vcap_layernorm_dispatch(int out_dt, const float* x, long ldx, void* y
   if (rows <= 0) return hipSuccess;
   const dim3 grid((rows + 3) / 4), block(256);
   const bool vec = (D % 256 == 0) && D <= 1024;
-  if (out_dt == VCAP_DT_BF16) {
+  if (out_dt == VCAP_DT_F16) {
+    if (vec)
+      hipLaunchKernelGGL((vcap_layernorm_kernel<f16_t, true>), grid, block, 0, s, x, ldx, (f16_t*)y, ldy, gamma,
+                         beta, rows, D, eps);
+    else
+      hipLaunchKernelGGL((vcap_layernorm_kernel<f16_t, false>), grid, block, 0, s, x, ldx, (f16_t*)y, ldy,
+                         gamma, beta, rows, D, eps);
+  } else if (out_dt == VCAP_DT_BF16) {
     if (vec)
       hipLaunchKernelGGL((vcap_layernorm_kernel<bf16_t, true>), grid, block, 0, s, x, ldx, (bf16_t*)y, ldy, gamma,
                          beta, rows, D, eps);

@@ -41,7 +41,7 @@ int hip_fail(hipError_t e, const char* where) {
     if (_e != hipSuccess) return hip_fail(_e, where); \
   } while (0)
 
-size_t esize(int dt) { return dt == VCAP_DT_MXFP8 ? 1 : dt == VCAP_DT_BF16 ? 2 : 4; }
+size_t esize(int dt) { return vcap_dt_size(dt); }
 size_t mx_scale_bytes(int rows, int K) { return (size_t)(K / 128) * (size_t)((rows + 255) / 256) * 1024; }
 size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -142,7 +142,7 @@ VitBufs carve_vit(Carver& c, const vcap_vit_desc* d, int B, int T) {
 
 int check_vit(const vcap_vit_desc* d) {
   if (!d || !d->layers) return fail(VCAP_E_ARG, "vit desc is null");
-  if (d->dtype != VCAP_DT_F32 && d->dtype != VCAP_DT_BF16 && d->dtype != VCAP_DT_MXFP8)
+  if (d->dtype != VCAP_DT_F32 && d->dtype != VCAP_DT_BF16 && d->dtype != VCAP_DT_MXFP8 && d->dtype != VCAP_DT_F16)
     return fail(VCAP_E_ARG, "vit dtype");
   if (d->heads * 64 != d->dim) return fail(VCAP_E_UNSUPPORTED, "vit head_dim must be 64");
   const int ka = vcap_gemm_k_align(d->dtype);
@@ -659,10 +659,31 @@ int vcap_gemm(int in_dtype, int out_dtype, const void* A, int64_t lda, const voi
   if (res_mode && !res) return fail(VCAP_E_ARG, "vcap_gemm: residual pointer missing");
   if ((res_mode == 2 || G) && G <= 0) return fail(VCAP_E_ARG, "vcap_gemm: row group G must be > 0");
   if (res_mode && out_dtype != VCAP_DT_F32) return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: residual needs f32 output");
+  if (in_dtype == VCAP_DT_F16 && out_dtype != VCAP_DT_F16 && out_dtype != VCAP_DT_F32)
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: f16 operands write f16 or f32");
   GemmEpi e{bias, res, (long)ldr, act, res_mode, G, Gs, goff, roff};
   g_err.clear();
   VCAP_TRY(vcap_gemm_dispatch(in_dtype, out_dtype, A, lda, W, ldw, C, ldc, M, N, K, e, (hipStream_t)stream),
            "vcap_gemm");
+  return 0;
+}
+
+int vcap_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc,
+                     int M, int N, int K, const float* bias, int G, int Gs, void* workspace, size_t ws_bytes,
+                     int* splits_out, void* stream) {
+  if (!A || !W || !C || !bias || !workspace || M <= 0 || N <= 0 || K <= 0 || G < 0 || (G && Gs < G))
+    return fail(VCAP_E_ARG, "vcap_gemm_splitk: bad arguments");
+  if (in_dtype != VCAP_DT_BF16 && in_dtype != VCAP_DT_F16)
+    return fail(VCAP_E_ARG, "vcap_gemm_splitk: operands must be VCAP_DT_BF16 or VCAP_DT_F16");
+  if (K % vcap_gemm_k_align(in_dtype)) return fail(VCAP_E_UNSUPPORTED, "vcap_gemm_splitk: K must be a multiple of 64");
+  if (N % 4 || ldc % 4 || ((uintptr_t)C & 15) || ((uintptr_t)workspace & 15))
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm_splitk: N, ldc in whole 16-byte vectors; C and workspace 16-byte aligned");
+  if (ws_bytes < (size_t)8 * M * N * sizeof(float)) return fail(VCAP_E_WORKSPACE, "vcap_gemm_splitk: workspace < 8*M*N*4 bytes");
+  GemmEpi e{bias, C, (long)ldc, 0, 1, G, Gs, 0, 0, nullptr, nullptr, nullptr, (float*)workspace, ws_bytes};
+  g_err.clear();
+  VCAP_TRY(vcap_gemm_dispatch(in_dtype, VCAP_DT_F32, A, lda, W, ldw, C, ldc, M, N, K, e, (hipStream_t)stream),
+           "vcap_gemm_splitk");
+  if (splits_out) *splits_out = vcap_gemm_last_splits();
   return 0;
 }
 
@@ -797,17 +818,24 @@ int vcap_vit_attention(int dtype, const void* qkv, void* out, int frames, int to
   return 0;
 }
 
-int vcap_vit_qkv_attention(const void* xn, const void* wqkv, const float* bqkv, void* out, int frames, int tokens,
-                           int heads, int cls_only, void* stream) {
+int vcap_vit_qkv_attention_dt(int dtype, const void* xn, const void* wqkv, const float* bqkv, void* out, int frames,
+                              int tokens, int heads, int cls_only, void* stream) {
   if (!xn || !wqkv || !bqkv || !out || frames <= 0 || tokens <= 0 || heads <= 0)
     return fail(VCAP_E_ARG, "vcap_vit_qkv_attention: bad arguments");
-  if (!vcap_vit_qkv_attention_supported(VCAP_DT_BF16, tokens, heads))
+  if (dtype != VCAP_DT_BF16 && dtype != VCAP_DT_F16)
+    return fail(VCAP_E_ARG, "vcap_vit_qkv_attention: dtype must be VCAP_DT_BF16 or VCAP_DT_F16");
+  if (!vcap_vit_qkv_attention_supported(dtype, tokens, heads))
     return fail(VCAP_E_UNSUPPORTED, "vcap_vit_qkv_attention: needs 192 < tokens <= 208 (ViT-B/16) or 256 < tokens <= 272 (ViT-L/14) "
                 "and heads*64 <= 4096");
-  VCAP_TRY(vcap_vit_qkv_attention_dispatch(xn, wqkv, bqkv, out, frames, tokens, heads, cls_only ? 1 : 0,
+  VCAP_TRY(vcap_vit_qkv_attention_dispatch(dtype, xn, wqkv, bqkv, out, frames, tokens, heads, cls_only ? 1 : 0,
                                            (hipStream_t)stream),
            "vcap_vit_qkv_attention");
   return 0;
+}
+
+int vcap_vit_qkv_attention(const void* xn, const void* wqkv, const float* bqkv, void* out, int frames, int tokens,
+                           int heads, int cls_only, void* stream) {
+  return vcap_vit_qkv_attention_dt(VCAP_DT_BF16, xn, wqkv, bqkv, out, frames, tokens, heads, cls_only, stream);
 }
 
 int vcap_vit_attention_mx(const void* qkv, void* out, uint8_t* out_scales, int frames, int tokens, int heads,
@@ -906,7 +934,7 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
     if (vit_layer_fused(d, ly)) {
       // QKV projection + attention in one kernel: q / k / v stay on chip
       ProbeScope ps(probe_attn, s, M);
-      VCAP_TRY(vcap_vit_qkv_attention_dispatch(w.xn, ly.qkv_w, ly.qkv_b, w.attn, BT, N, d->heads, last, s),
+      VCAP_TRY(vcap_vit_qkv_attention_dispatch(adt, w.xn, ly.qkv_w, ly.qkv_b, w.attn, BT, N, d->heads, last, s),
                "qkv_attention");
     } else {
       {
@@ -962,7 +990,7 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
   VCAP_TRY(vcap_vit_head_prefix_dispatch(w.x, B, T, N, D, d->norm_g, d->norm_b, d->ln_eps, d->proj_w, d->proj_b,
                                          d->video_dim, ls, iw, pd ? pd->mapper_w : nullptr,
                                          pd ? pd->mapper_b : nullptr, MO, enc_out, prefix_out, nullptr,
-                                         (float*)w.xn, s),
+                                         (float*)w.xn, s, dt == VCAP_DT_F16),
            "head_prefix");
   return 0;
 }

@@ -30,6 +30,17 @@ VCAP_DEV uint32_t pack_bf2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_){lo, hi}, bf16x2_t));
 }
 
+// IEEE binary16 (torch.float16), the reference's autocast dtype: a distinct C++ type beside bf16_t
+// (a uint16_t) so templates and the mfma_frag overloads tell the two 2-byte formats apart.
+typedef _Float16 f16_t;
+// two f32 -> packed f16x2, round-to-nearest-even: the vector conversion selects one v_cvt_pk_f16_f32
+// (like pack_bf2, not inline asm).  Overflow gives +-inf and subnormal results are rounded, not
+// flushed, as torch's .half() does; no clamp.
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+VCAP_DEV uint32_t pack_h2(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_){lo, hi}, f16x2_t));
+}
+
 template <typename T> struct Num;
 template <> struct Num<float> {
   static VCAP_DEV float to_f(float v) { return v; }
@@ -38,6 +49,40 @@ template <> struct Num<float> {
 template <> struct Num<bf16_t> {
   static VCAP_DEV float to_f(bf16_t v) { return bf2f(v); }
   static VCAP_DEV bf16_t from_f(float v) { return f2bf(v); }
+};
+template <> struct Num<f16_t> {
+  static VCAP_DEV float to_f(f16_t v) { return (float)v; }
+  static VCAP_DEV f16_t from_f(float v) { return (f16_t)v; }
+};
+
+// packed f32x2 -> 2 x T conversion of the 2-byte element types
+template <typename T> struct Pack2;
+template <> struct Pack2<bf16_t> {
+  static VCAP_DEV uint32_t pack(float lo, float hi) { return pack_bf2(lo, hi); }
+};
+template <> struct Pack2<f16_t> {
+  static VCAP_DEV uint32_t pack(float lo, float hi) { return pack_h2(lo, hi); }
+};
+// 1.0 in both halves of a dword
+template <typename T> struct Ones2;
+template <> struct Ones2<bf16_t> { static constexpr uint32_t v = 0x3F803F80u; };
+template <> struct Ones2<f16_t> { static constexpr uint32_t v = 0x3C003C00u; };
+
+// torch.autocast(float16) makes every Linear return fp16: with f16 operands a GEMM epilogue rounds
+// accumulator + bias to fp16 where autocast does (before the f32 residual add, before and after the
+// GELU).  Identity for the bf16 / f32 operand types, whose arithmetic is unchanged.
+template <typename T> struct Autocast {
+  static constexpr bool kRound = false;
+  static VCAP_DEV float rnd(float v) { return v; }
+  static VCAP_DEV f32x4 rnd4(f32x4 v) { return v; }
+};
+template <> struct Autocast<f16_t> {
+  static constexpr bool kRound = true;
+  static VCAP_DEV float rnd(float v) { return (float)(f16_t)v; }
+  static VCAP_DEV f32x4 rnd4(f32x4 v) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+    return __builtin_convertvector(__builtin_convertvector(v, f16x4_t), f32x4);
+  }
 };
 
 // LayerNorm arithmetic of the decode kernels in ONE fixed operation order.  Left to
@@ -198,6 +243,12 @@ VCAP_DEV f32x4 mfma_frag(const u32x4& a, const u32x4& b, f32x4 c, bf16_t*) {
   bf16x8 bv = __builtin_bit_cast(bf16x8, b);
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, c, 0, 0, 0);
 }
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;  // MFMA 16x16x32 f16 A/B fragment (bf16's layout)
+VCAP_DEV f32x4 mfma_frag(const u32x4& a, const u32x4& b, f32x4 c, f16_t*) {
+  f16x8 av = __builtin_bit_cast(f16x8, a);
+  f16x8 bv = __builtin_bit_cast(f16x8, b);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, c, 0, 0, 0);
+}
 VCAP_DEV f32x4 mfma_frag(const u32x4& a, const u32x4& b, f32x4 c, float*) {
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
@@ -294,5 +345,12 @@ VCAP_DEV void mfma_mx_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" :::
 template <typename T> struct Frag { static constexpr int kElems = 16 / sizeof(T); };
 
 #ifndef VCAP_H_
-enum { VCAP_DT_F32 = 0, VCAP_DT_BF16 = 1, VCAP_DT_MXFP8 = 2 };  // mirrors include/vcap.h
+enum { VCAP_DT_F32 = 0, VCAP_DT_BF16 = 1, VCAP_DT_MXFP8 = 2, VCAP_DT_F16 = 3 };  // mirrors include/vcap.h
 #endif
+
+// bytes per element of a dtype code (0: not a dtype); the one place that knows the element sizes
+inline size_t vcap_dt_size(int dt) {
+  return dt == VCAP_DT_F32 ? 4 : (dt == VCAP_DT_BF16 || dt == VCAP_DT_F16) ? 2 : dt == VCAP_DT_MXFP8 ? 1 : 0;
+}
+// the two 2-byte MFMA operand formats (same kernels, tile shapes and K steps)
+inline bool vcap_dt_is16(int dt) { return dt == VCAP_DT_BF16 || dt == VCAP_DT_F16; }

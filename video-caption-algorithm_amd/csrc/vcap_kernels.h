@@ -110,6 +110,8 @@ int vcap_sample_max_top_k();
 hipError_t vcap_gemm_dispatch(int in_dt, int out_dt, const void* A, long lda, const void* W, long ldw, void* C,
                               long ldc, int M, int N, int K, const GemmEpi& epi, hipStream_t s);
 int vcap_gemm_k_align(int in_dt);
+// K splits (grid.y) of this thread's latest 128x128-kernel launch; 1 = unsplit
+int vcap_gemm_last_splits();
 // CUs a launch on stream s may use (its CU mask, else the device's CU count)
 int vcap_stream_cus(hipStream_t s);
 // CUs of the current device (launch plans that must not depend on a stream's CU mask)
@@ -128,11 +130,11 @@ hipError_t vcap_layernorm_dispatch(int out_dt, const float* x, long ldx, void* y
 // cls_only: only the class-token query of each (frame, head), written to compact row `frame`
 hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int BT, int N, int H, hipStream_t s,
                                        int cls_only = 0);
-// fused QKV projection + attention (bf16, 192 < N <= 208 or 256 < N <= 272): xn [BT*N, H*64] LayerNorm output, wqkv
+// fused QKV projection + attention (bf16 or f16, 192 < N <= 208 or 256 < N <= 272): xn [BT*N, H*64] LayerNorm output, wqkv
 // [3*H*64, H*64], bqkv [3*H*64] -> out as vcap_vit_attention_dispatch's
 bool vcap_vit_qkv_attention_supported(int dt, int N, int H);
-hipError_t vcap_vit_qkv_attention_dispatch(const void* xn, const void* wqkv, const float* bqkv, void* out, int BT,
-                                           int N, int H, int cls_only, hipStream_t s);
+hipError_t vcap_vit_qkv_attention_dispatch(int dt, const void* xn, const void* wqkv, const float* bqkv, void* out,
+                                           int BT, int N, int H, int cls_only, hipStream_t s);
 hipError_t vcap_vit_attention_mx_dispatch(const void* qkv, void* out, uint8_t* oscale, int BT, int N, int H,
                                           hipStream_t s, int cls_only = 0);
 hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, float* x, const float* cls,
@@ -140,7 +142,8 @@ hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, fl
 hipError_t vcap_vit_head_prefix_dispatch(const float* x, int B, int T, int N, int D, const float* ng, const float* nb,
                                          float neps, const float* pw, const float* pb, int VD, float ln_scale,
                                          float in_weight, const float* mw, const float* mb, int MO, float* enc_out,
-                                         float* prefix, const float* emb_in, float* emb_scratch, hipStream_t s);
+                                         float* prefix, const float* emb_in, float* emb_scratch, hipStream_t s,
+                                         int f16_head = 0);
 hipError_t vcap_vit_pool_dispatch(int dt, const void* x, void* y, int B, int T, int tokens, int C, int gap,
                                   hipStream_t s);
 hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs& a, int* nblk_out, hipStream_t s);

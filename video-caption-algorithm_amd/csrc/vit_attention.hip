@@ -119,9 +119,9 @@ __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __rest
     if constexpr (sizeof(T) == 2) {
 #pragma unroll
       for (int c = 0; c < KT / 2; ++c) {
-        const u32x4 pf = (u32x4){pack_bf2(st[2 * c][0], st[2 * c][1]), pack_bf2(st[2 * c][2], st[2 * c][3]),
-                                 pack_bf2(st[2 * c + 1][0], st[2 * c + 1][1]),
-                                 pack_bf2(st[2 * c + 1][2], st[2 * c + 1][3])};
+        const u32x4 pf = (u32x4){Pack2<T>::pack(st[2 * c][0], st[2 * c][1]), Pack2<T>::pack(st[2 * c][2], st[2 * c][3]),
+                                 Pack2<T>::pack(st[2 * c + 1][0], st[2 * c + 1][1]),
+                                 Pack2<T>::pack(st[2 * c + 1][2], st[2 * c + 1][3])};
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           const T* vrow = Vt + (dt * 16 + fr) * VS + 32 * c + 4 * fg;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __rest
       for (int dt = 0; dt < 4; ++dt) {
         const f32x4 v = o[dt] * inv;  // O^T[d = dt*16 + 4*fg + r][q]
         if constexpr (sizeof(T) == 2) {
-          *reinterpret_cast<u32x2*>(orow + dt * 16 + 4 * fg) = (u32x2){pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
+          *reinterpret_cast<u32x2*>(orow + dt * 16 + 4 * fg) = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
         } else {
           *reinterpret_cast<f32x4*>(orow + dt * 16 + 4 * fg) = v;
         }
@@ -159,7 +159,10 @@ __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16 path (the benchmark dtype).  Same S^T = K Q^T formulation and exact in-register softmax,
+// bf16 path (the benchmark dtype; templated on the 2-byte element type T, so the f16 mode runs the
+// same schedule with v_mfma_f32_16x16x32_f16 and v_cvt_pk_f16_f32).  The names below keep `bf16`
+// (vcap_vit_attention_bf16_kernel, attn_bf16_qtile, launch_attn_bf16: the symbols the profiles and
+// tools know); read it as "the 2-byte element path", T = bf16_t or f16_t.  Same S^T = K Q^T formulation and exact in-register softmax,
 // but nothing passes through VGPRs on the way to LDS and nothing is transposed by stores:
 //  * K and V rows arrive by LDS-DMA (global_load_lds_dwordx4, 1 KiB = 8 rows per wave
 //    instruction) into [key][64] images with the 16-byte-chunk XOR swizzle slot = c ^ (key & 7)
@@ -181,7 +184,8 @@ VCAP_DEV void glds16_attn(const void* g, char* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-VCAP_DEV uint32_t cvt_pk_bf16(float lo, float hi) { return pack_bf2(lo, hi); }
+template <typename T>
+VCAP_DEV uint32_t cvt_pk16(float lo, float hi) { return Pack2<T>::pack(lo, hi); }
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
@@ -195,7 +199,7 @@ VCAP_DEV u32x2 tr_read(const char* p) {
 // and 1 / rowsum (lane (fr, fg) holds dims dt*16 + 4*fg + r of query fr).
 // KE: key tiles that can hold real keys (KT or KT - 1: with N <= 16 (KT - 1) the last tile is all
 // padding, kept only as the zero half of the last 32-key PV chunk - no S, max or exp for it).
-template <int KT, int KE>
+template <int KT, int KE, typename T>
 VCAP_DEV void attn_bf16_qtile(const char* Ks, const char* Vs, const u32x4 (&qf)[2], int N, f32x4 (&o)[4],
                               float& inv) {
   const int lane = threadIdx.x & 63;
@@ -211,7 +215,7 @@ VCAP_DEV void attn_bf16_qtile(const char* Ks, const char* Vs, const u32x4 (&qf)[
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + key * 128 + (((s * 4 + fg) ^ (key & 7)) << 4));
-      acc = mfma_frag(kf, qf[s], acc, (bf16_t*)nullptr);
+      acc = mfma_frag(kf, qf[s], acc, (T*)nullptr);
     }
     st[kt] = acc;  // keys kt*16 + 4*fg + r, query fr
   }
@@ -250,16 +254,16 @@ VCAP_DEV void attn_bf16_qtile(const char* Ks, const char* Vs, const u32x4 (&qf)[
   // 32c + 4g + j (j < 4) / 32c + 16 + 4g + (j - 4), matching the P^T fragment below
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  // S[q] = sum_key 1 * P^T[key][q]: every output row of this MFMA is the sum of the bf16 P the
+  // S[q] = sum_key 1 * P^T[key][q]: every output row of this MFMA is the sum of the rounded P the
   // PV products use (lane (fr, fg) gets query fr's sum in each element)
   f32x4 osum = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const u32x4 ones = (u32x4){0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
+  const u32x4 ones = (u32x4){Ones2<T>::v, Ones2<T>::v, Ones2<T>::v, Ones2<T>::v};  // 1.0 x 8
   const int qr = fr >> 2, p4 = fr & 3;
 #pragma unroll
   for (int c = 0; c < KT / 2; ++c) {
-    const u32x4 pf = (u32x4){cvt_pk_bf16(st[2 * c][0], st[2 * c][1]), cvt_pk_bf16(st[2 * c][2], st[2 * c][3]),
-                             cvt_pk_bf16(st[2 * c + 1][0], st[2 * c + 1][1]),
-                             cvt_pk_bf16(st[2 * c + 1][2], st[2 * c + 1][3])};
+    const u32x4 pf = (u32x4){cvt_pk16<T>(st[2 * c][0], st[2 * c][1]), cvt_pk16<T>(st[2 * c][2], st[2 * c][3]),
+                             cvt_pk16<T>(st[2 * c + 1][0], st[2 * c + 1][1]),
+                             cvt_pk16<T>(st[2 * c + 1][2], st[2 * c + 1][3])};
     const int r0 = 32 * c + 4 * fg + qr, r1 = r0 + 16;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -268,9 +272,9 @@ VCAP_DEV void attn_bf16_qtile(const char* Ks, const char* Vs, const u32x4 (&qf)[
       // keys 16 KE .. 16 KT - 1 are all padding (P = 0): not staged, a zero operand instead
       const u32x2 hi = (KE < KT && c == KT / 2 - 1) ? (u32x2){0u, 0u}
                                                     : tr_read(Vs + r1 * 128 + ((ch ^ (r1 & 7)) << 4) + 8 * (p4 & 1));
-      o[dt] = mfma_frag((u32x4){lo.x, lo.y, hi.x, hi.y}, pf, o[dt], (bf16_t*)nullptr);
+      o[dt] = mfma_frag((u32x4){lo.x, lo.y, hi.x, hi.y}, pf, o[dt], (T*)nullptr);
     }
-    osum = mfma_frag(ones, pf, osum, (bf16_t*)nullptr);
+    osum = mfma_frag(ones, pf, osum, (T*)nullptr);
   }
   const float sum = osum[0];
   inv = __builtin_amdgcn_rcpf(sum);
@@ -286,7 +290,7 @@ struct AttnOut {
   bool keep;
 };
 
-template <bool MXO>
+template <bool MXO, typename T>
 VCAP_DEV AttnOut attn_pack(const f32x4 (&o)[4], float inv, long row, bool keep) {
   const int lane = threadIdx.x & 63;
   AttnOut r;
@@ -322,8 +326,8 @@ VCAP_DEV AttnOut attn_pack(const f32x4 (&o)[4], float inv, long row, bool keep) 
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const f32x4 va = o[2 * k] * inv, vb = o[2 * k + 1] * inv;
-      const uint32_t a0 = cvt_pk_bf16(va.x, va.y), a1 = cvt_pk_bf16(va.z, va.w);
-      const uint32_t b0 = cvt_pk_bf16(vb.x, vb.y), b1 = cvt_pk_bf16(vb.z, vb.w);
+      const uint32_t a0 = cvt_pk16<T>(va.x, va.y), a1 = cvt_pk16<T>(va.z, va.w);
+      const uint32_t b0 = cvt_pk16<T>(vb.x, vb.y), b1 = cvt_pk16<T>(vb.z, vb.w);
       const uint32_t r0 = (uint32_t)xor16_i((int)(odd ? a0 : b0));
       const uint32_t r1 = (uint32_t)xor16_i((int)(odd ? a1 : b1));
       const u32x4 w = odd ? (u32x4){r0, r1, b0, b1} : (u32x4){a0, a1, r0, r1};
@@ -345,7 +349,7 @@ VCAP_DEV void attn_commit(const AttnOut& r, void* out, int D, int h, uint8_t* os
     *reinterpret_cast<u32x4*>((uint8_t*)out + r.row * D + h * 64 + 16 * fg) = r.w0;
   } else {
     const bool odd = (lane & 16) != 0;
-    bf16_t* orow = (bf16_t*)out + r.row * D + h * 64;
+    uint16_t* orow = (uint16_t*)out + r.row * D + h * 64;  // either 2-byte element type
     *reinterpret_cast<u32x4*>(orow + (odd ? 12 + 4 * fg : 4 * fg)) = r.w0;
     *reinterpret_cast<u32x4*>(orow + 32 + (odd ? 12 + 4 * fg : 4 * fg)) = r.w1;
   }
@@ -358,8 +362,8 @@ VCAP_DEV void attn_commit(const AttnOut& r, void* out, int D, int h, uint8_t* os
 // 39.1-39.7 vs 37.8-38.6 us at 128 frames, r03 (profiles/r03_attention_v_overlap_ab.txt): reverted.)
 // MXO: write the output as MXFP8 (e4m3 + E8M0 per 32 of the head's 64 dims) for an MXFP8 attn-proj
 // GEMM; oscale in the vcap_common.h layout over `groups` 256-row groups.
-template <int KT, int KE, int WAVES, bool MXO>
-__global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(const bf16_t* __restrict__ qkv,
+template <int KT, int KE, int WAVES, bool MXO, typename T>
+__global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(const T* __restrict__ qkv,
                                                                              void* __restrict__ out, int N, int H,
                                                                              uint8_t* __restrict__ oscale,
                                                                              int groups, int cls_only) {
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
   const int bt = bh / H, h = bh - bt * H;
   const int D = H * 64;
   const long ld = 3L * D;
-  const bf16_t* base = qkv + (long)bt * N * ld + h * 64;
+  const T* base = qkv + (long)bt * N * ld + h * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
@@ -384,7 +388,7 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
   for (int blk = wave; blk < NS / 8; blk += WAVES) {
     const int r = blk * 8 + (lane >> 3);
     const int c = (lane & 7) ^ (r & 7);
-    const bf16_t* src = base + (long)min(r, N - 1) * ld + c * 8;
+    const T* src = base + (long)min(r, N - 1) * ld + c * 8;
     glds16_attn(src + D, Ks + blk * 1024);
     glds16_attn(src + 2 * D, Vs + blk * 1024);
   }
@@ -407,28 +411,28 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
     if (qt >= qtiles) break;
     f32x4 o[4];
     float inv;
-    attn_bf16_qtile<KT, KE>(Ks, Vs, qf[i], N, o, inv);
+    attn_bf16_qtile<KT, KE, T>(Ks, Vs, qf[i], N, o, inv);
     const int q = qt * 16 + fr;
     const bool keep = q < N && (!cls_only || q == 0);
     const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<MXO>(attn_pack<MXO>(o, inv, row, keep), out, D, h, oscale, groups);
+    attn_commit<MXO>(attn_pack<MXO, T>(o, inv, row, keep), out, D, h, oscale, groups);
   }
 }
 
-template <int KT, int KE, int WAVES, bool MXO>
+template <int KT, int KE, int WAVES, bool MXO, typename T>
 static hipError_t launch_attn_bf16(const void* qkv, void* out, int BT, int N, int H, uint8_t* oscale, int cls_only,
                                    hipStream_t s) {
   const size_t lds = (size_t)KE * 16 * 128 * 2;  // 53 KiB at KE = 13: three workgroups per CU
   static bool configured = false;
   if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO>,
+    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO, T>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     configured = true;
   }
   const int groups = ((cls_only ? BT : BT * N) + 255) / 256;  // scale rows = output rows
-  hipLaunchKernelGGL((vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO>), dim3(BT * H), dim3(WAVES * 64), lds, s,
-                     (const bf16_t*)qkv, out, N, H, oscale, groups, cls_only);
+  hipLaunchKernelGGL((vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO, T>), dim3(BT * H), dim3(WAVES * 64), lds, s,
+                     (const T*)qkv, out, N, H, oscale, groups, cls_only);
   return hipGetLastError();
 }
 
@@ -450,15 +454,15 @@ static hipError_t launch_attn(const void* qkv, void* out, int BT, int N, int H, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused QKV projection + attention (bf16, ViT-B/16 frame: 197 tokens, head_dim 64).  One workgroup
-// (8 waves) per (frame, head): it computes the head's 192 q / k / v features of the frame's 208
-// (padded) tokens from the LayerNorm output and the head's 192 weight rows, writes them as bf16
+// Fused QKV projection + attention (2-byte elements T = bf16 or f16, ViT-B/16 frame: 197 tokens,
+// head_dim 64).  One workgroup (8 waves) per (frame, head): it computes the head's 192 q / k / v features of the frame's 208
+// (padded) tokens from the LayerNorm output and the head's 192 weight rows, writes them as T
 // straight into the attention's LDS images and runs the attention above on them - q / k / v never
-// leave the CU (the unfused pair writes 3 x 768 bf16 per token to HBM and reads them back).
+// leave the CU (the unfused pair writes 3 x 768 elements per token to HBM and reads them back).
 //  * GEMM: C^T[feature][token] with the weight fragment as the MFMA A operand (each lane ends up
 //    with 4 consecutive features of one token = 8 contiguous bytes of a [token][64] image) and the
 //    K order of vcap_gemm256_kernel (32-wide sub-steps, lane group g = K [8g, 8g + 8)), so every
-//    q / k / v value, its bias add and its bf16 rounding are those of the unfused QKV GEMM and the
+//    q / k / v value, its bias add and its rounding to T are those of the unfused QKV GEMM and the
 //    output is bit-identical to QKV GEMM + vcap_vit_attention_bf16_kernel;
 //  * waves 4 (feature groups of 3 tiles) x 2 (token groups of 7 / 6 tiles): 21 / 18 16x16
 //    accumulators per wave;
@@ -499,10 +503,11 @@ VCAP_DEV void qa_wait_older(bool older) {
   }
 }
 
-__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_t* __restrict__ xn,
-                                                                     const bf16_t* __restrict__ wqkv,
+template <typename T>
+__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __restrict__ xn,
+                                                                     const T* __restrict__ wqkv,
                                                                      const float* __restrict__ bqkv,
-                                                                     bf16_t* __restrict__ out, int BT, int N, int H,
+                                                                     T* __restrict__ out, int BT, int N, int H,
                                                                      int cls_only) {
   using namespace qa;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -537,7 +542,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_
     const int blk = min(25 * tgrp + wig + 4 * i, BLKS - 1);
     const int lr = blk * 8 + (lane >> 3);
     const int c = (lane & 7) ^ (lr & 7);
-    const bf16_t* p;
+    const T* p;
     if (lr < RT) {
       p = xn + ((long)bt * N + min(lr, N - 1)) * D;
     } else {
@@ -602,7 +607,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_
       for (int j = 0; j < 7; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (j < ntt) acc[i][j] = mfma_frag(wf[s][i], tf[s][j], acc[i][j], (bf16_t*)nullptr);
+          if (j < ntt) acc[i][j] = mfma_frag(wf[s][i], tf[s][j], acc[i][j], (T*)nullptr);
     __builtin_amdgcn_s_setprio(0);
     qa_barrier();
   }
@@ -623,7 +628,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_
       if (j < ntt) {
         const int tok = (t0 + j) * 16 + fr;
         const f32x4 v = acc[i][j] + bias;
-        const u32x2 p = (u32x2){pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
+        const u32x2 p = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
         *reinterpret_cast<u32x2*>(img + tok * 128 + (((d0 >> 3) ^ (tok & 7)) << 4) + (d0 & 7) * 2) = p;
       }
     }
@@ -644,11 +649,11 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_
       qf[s] = *reinterpret_cast<const u32x4*>(Qs + qrow * 128 + (((s * 4 + fg) ^ (qrow & 7)) << 4));
     f32x4 o[4];
     float inv;
-    attn_bf16_qtile<14, 13>(Ks, Vs, qf, N, o, inv);
+    attn_bf16_qtile<14, 13, T>(Ks, Vs, qf, N, o, inv);
     const int q = qt * 16 + fr;
     const bool keep = q < N && (!cls_only || q == 0);
     const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<false>(attn_pack<false>(o, inv, row, keep), out, D, h, nullptr, 0);
+    attn_commit<false>(attn_pack<false, T>(o, inv, row, keep), out, D, h, nullptr, 0);
   }
 }
 
@@ -661,7 +666,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const bf16_
 // from group 0's read phase kt on, and group 1 reads it one barrier after group 0: so group 0 (the
 // leading group) stages every weight block, one K-tile ahead, and waits for them at the end of its MFMA
 // phase; the token blocks go two K-tiles ahead, 5 of 34 per K-tile from group 0 and 29 from group 1
-// (29 pieces per group: 8 / 7 / 7 / 7 per wave).  Arithmetic, K order, bias add and bf16 rounding are
+// (29 pieces per group: 8 / 7 / 7 / 7 per wave).  Arithmetic, K order, bias add and rounding to T are
 // those of vcap_vit_qkv_attention_kernel, so the output is bit-identical to the unfused QKV GEMM +
 // vcap_vit_attention_bf16_kernel<18, 17> pair.
 namespace qb {
@@ -690,10 +695,11 @@ VCAP_DEV void qb_vm_wait(int n) {
   }
 }
 
-__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const bf16_t* __restrict__ xn,
-                                                                       const bf16_t* __restrict__ wqkv,
+template <typename T>
+__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* __restrict__ xn,
+                                                                       const T* __restrict__ wqkv,
                                                                        const float* __restrict__ bqkv,
-                                                                       bf16_t* __restrict__ out, int BT, int N, int H,
+                                                                       T* __restrict__ out, int BT, int N, int H,
                                                                        int cls_only) {
   using namespace qb;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -731,7 +737,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const bf1
     const int blk = wblk ? li : (tgrp == 0 ? (TBLK - G0_TOK) + (li - WBLK) : li);  // group 0: tokens 29..33
     const int lr = blk * 8 + (lane >> 3);       // row within its region
     const int c = (lane & 7) ^ (lr & 7);
-    const bf16_t* p;
+    const T* p;
     if (!wblk) {
       p = xn + ((long)bt * N + min(lr, N - 1)) * D;
     } else {
@@ -802,7 +808,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const bf1
       for (int j = 0; j < 9; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (j < ntt) acc[i][j] = mfma_frag(wf[s2][i], tf[s2][j], acc[i][j], (bf16_t*)nullptr);
+          if (j < ntt) acc[i][j] = mfma_frag(wf[s2][i], tf[s2][j], acc[i][j], (T*)nullptr);
     __builtin_amdgcn_s_setprio(0);
     if (w_now) qb_vm_wait(t_now);  // group 0: the weights of kt + 1 landed before group 1 reads them
     qa_barrier();
@@ -824,7 +830,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const bf1
       if (j < ntt) {
         const int tok = (t0 + j) * 16 + fr;
         const f32x4 v = acc[i][j] + bias;
-        const u32x2 pk = (u32x2){pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
+        const u32x2 pk = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
         *reinterpret_cast<u32x2*>(img + tok * 128 + (((d0 >> 3) ^ (tok & 7)) << 4) + (d0 & 7) * 2) = pk;
       }
     }
@@ -845,58 +851,65 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const bf1
       qf[s2] = *reinterpret_cast<const u32x4*>(Qs + qrow * 128 + (((s2 * 4 + fg) ^ (qrow & 7)) << 4));
     f32x4 o[4];
     float inv;
-    attn_bf16_qtile<18, 17>(Ks, Vs, qf, N, o, inv);
+    attn_bf16_qtile<18, 17, T>(Ks, Vs, qf, N, o, inv);
     const int q = qt * 16 + fr;
     const bool keep = q < N && (!cls_only || q == 0);
     const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<false>(attn_pack<false>(o, inv, row, keep), out, D, h, nullptr, 0);
+    attn_commit<false>(attn_pack<false, T>(o, inv, row, keep), out, D, h, nullptr, 0);
   }
 }
 
 bool vcap_vit_qkv_attention_supported(int dt, int N, int H) {
-  return dt == VCAP_DT_BF16 && ((N > 12 * 16 && N <= 13 * 16) || (N > 16 * 16 && N <= 17 * 16)) && H > 0 &&
+  return vcap_dt_is16(dt) && ((N > 12 * 16 && N <= 13 * 16) || (N > 16 * 16 && N <= 17 * 16)) && H > 0 &&
          H * 64 <= 4096;
 }
 
-hipError_t vcap_vit_qkv_attention_dispatch(const void* xn, const void* wqkv, const float* bqkv, void* out, int BT,
-                                           int N, int H, int cls_only, hipStream_t s) {
-  if (!vcap_vit_qkv_attention_supported(VCAP_DT_BF16, N, H) || BT <= 0 || !bqkv) return hipErrorInvalidValue;
+template <typename T>
+static hipError_t launch_qkv_attention(const void* xn, const void* wqkv, const float* bqkv, void* out, int BT, int N,
+                                       int H, int cls_only, hipStream_t s) {
   if (N > 13 * 16) {  // ViT-L/14: 17 token tiles
     static bool configured_l = false;
     if (!configured_l) {
-      hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_l_kernel,
+      hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_l_kernel<T>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, qb::LDS);
       if (e != hipSuccess) return e;
       configured_l = true;
     }
-    hipLaunchKernelGGL(vcap_vit_qkv_attention_l_kernel, dim3(BT * H), dim3(512), qb::LDS, s, (const bf16_t*)xn,
-                       (const bf16_t*)wqkv, bqkv, (bf16_t*)out, BT, N, H, cls_only);
+    hipLaunchKernelGGL(vcap_vit_qkv_attention_l_kernel<T>, dim3(BT * H), dim3(512), qb::LDS, s, (const T*)xn,
+                       (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
     return hipGetLastError();
   }
   static bool configured = false;
   if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_kernel,
+    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_kernel<T>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, qa::LDS);
     if (e != hipSuccess) return e;
     configured = true;
   }
-  hipLaunchKernelGGL(vcap_vit_qkv_attention_kernel, dim3(BT * H), dim3(512), qa::LDS, s, (const bf16_t*)xn,
-                     (const bf16_t*)wqkv, bqkv, (bf16_t*)out, BT, N, H, cls_only);
+  hipLaunchKernelGGL(vcap_vit_qkv_attention_kernel<T>, dim3(BT * H), dim3(512), qa::LDS, s, (const T*)xn,
+                     (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
   return hipGetLastError();
 }
 
+hipError_t vcap_vit_qkv_attention_dispatch(int dt, const void* xn, const void* wqkv, const float* bqkv, void* out,
+                                           int BT, int N, int H, int cls_only, hipStream_t s) {
+  if (!vcap_vit_qkv_attention_supported(dt, N, H) || BT <= 0 || !bqkv) return hipErrorInvalidValue;
+  if (dt == VCAP_DT_F16) return launch_qkv_attention<f16_t>(xn, wqkv, bqkv, out, BT, N, H, cls_only, s);
+  return launch_qkv_attention<bf16_t>(xn, wqkv, bqkv, out, BT, N, H, cls_only, s);
+}
+
 // bf16 kernel choice by padded key count; KE = key tiles that can hold real keys
-template <bool MXO>
+template <bool MXO, typename T>
 static hipError_t attn_bf16_dispatch(const void* qkv, void* out, uint8_t* oscale, int BT, int N, int H,
                                      int cls_only, hipStream_t s) {
   switch (((N + 31) / 32) * 2) {  // keys padded to a multiple of 32
-    case 2: return launch_attn_bf16<2, 2, 4, MXO>(qkv, out, BT, N, H, oscale, cls_only, s);
+    case 2: return launch_attn_bf16<2, 2, 4, MXO, T>(qkv, out, BT, N, H, oscale, cls_only, s);
     case 14:
-      if (N <= 13 * 16) return launch_attn_bf16<14, 13, 8, MXO>(qkv, out, BT, N, H, oscale, cls_only, s);
-      return launch_attn_bf16<14, 14, 8, MXO>(qkv, out, BT, N, H, oscale, cls_only, s);
+      if (N <= 13 * 16) return launch_attn_bf16<14, 13, 8, MXO, T>(qkv, out, BT, N, H, oscale, cls_only, s);
+      return launch_attn_bf16<14, 14, 8, MXO, T>(qkv, out, BT, N, H, oscale, cls_only, s);
     case 18:
-      if (N <= 17 * 16) return launch_attn_bf16<18, 17, 8, MXO>(qkv, out, BT, N, H, oscale, cls_only, s);
-      return launch_attn_bf16<18, 18, 8, MXO>(qkv, out, BT, N, H, oscale, cls_only, s);
+      if (N <= 17 * 16) return launch_attn_bf16<18, 17, 8, MXO, T>(qkv, out, BT, N, H, oscale, cls_only, s);
+      return launch_attn_bf16<18, 18, 8, MXO, T>(qkv, out, BT, N, H, oscale, cls_only, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -904,7 +917,19 @@ static hipError_t attn_bf16_dispatch(const void* qkv, void* out, uint8_t* oscale
 hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int BT, int N, int H, hipStream_t s,
                                        int cls_only) {
   if (N <= 0 || N > 288) return hipErrorInvalidValue;
-  if (dt == VCAP_DT_BF16) return attn_bf16_dispatch<false>(qkv, out, nullptr, BT, N, H, cls_only, s);
+  if (dt == VCAP_DT_BF16) return attn_bf16_dispatch<false, bf16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
+  if (dt == VCAP_DT_F16) {
+    // the ViT frame sizes run the bf16 path's schedule; any other token count the generic kernel
+    // (keys padded to 64 / 128 / 192 / 256 and masked)
+    const int kt = ((N + 31) / 32) * 2;
+    if (kt == 2 || kt == 14 || kt == 18)
+      return attn_bf16_dispatch<false, f16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
+    if (kt <= 4) return launch_attn<f16_t, 4>(qkv, out, BT, N, H, cls_only, s);
+    if (kt <= 8) return launch_attn<f16_t, 8>(qkv, out, BT, N, H, cls_only, s);
+    if (kt <= 12) return launch_attn<f16_t, 12>(qkv, out, BT, N, H, cls_only, s);
+    return launch_attn<f16_t, 16>(qkv, out, BT, N, H, cls_only, s);
+  }
+  if (dt != VCAP_DT_F32) return hipErrorInvalidValue;
   switch (((N + 31) / 32) * 2) {
     case 2: return launch_attn<float, 2>(qkv, out, BT, N, H, cls_only, s);
     case 14: return launch_attn<float, 14>(qkv, out, BT, N, H, cls_only, s);
@@ -917,5 +942,5 @@ hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int B
 hipError_t vcap_vit_attention_mx_dispatch(const void* qkv, void* out, uint8_t* oscale, int BT, int N, int H,
                                           hipStream_t s, int cls_only) {
   if (N <= 0 || N > 288 || !oscale) return hipErrorInvalidValue;
-  return attn_bf16_dispatch<true>(qkv, out, oscale, BT, N, H, cls_only, s);
+  return attn_bf16_dispatch<true, bf16_t>(qkv, out, oscale, BT, N, H, cls_only, s);
 }

@@ -64,8 +64,8 @@ __global__ __launch_bounds__(256) void vcap_patchify8_kernel(const float* __rest
   }
   T* dst = patches + row * Kp + k;
   if constexpr (sizeof(T) == 2) {
-    *reinterpret_cast<u32x4*>(dst) = (u32x4){pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y),
-                                             pack_bf2(b.z, b.w)};
+    *reinterpret_cast<u32x4*>(dst) = (u32x4){Pack2<T>::pack(a.x, a.y), Pack2<T>::pack(a.z, a.w),
+                                             Pack2<T>::pack(b.x, b.y), Pack2<T>::pack(b.z, b.w)};
   } else {
     *reinterpret_cast<f32x4*>(dst) = a;
     *reinterpret_cast<f32x4*>(dst + 4) = b;
@@ -87,6 +87,9 @@ hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, fl
     if (dt == VCAP_DT_BF16)
       hipLaunchKernelGGL((vcap_patchify8_kernel<bf16_t>), grid, dim3(256), 0, s, frames, (bf16_t*)patches, BT, img, p,
                          Kp);
+    else if (dt == VCAP_DT_F16)
+      hipLaunchKernelGGL((vcap_patchify8_kernel<f16_t>), grid, dim3(256), 0, s, frames, (f16_t*)patches, BT, img, p,
+                         Kp);
     else
       hipLaunchKernelGGL((vcap_patchify8_kernel<float>), grid, dim3(256), 0, s, frames, (float*)patches, BT, img, p,
                          Kp);
@@ -96,6 +99,9 @@ hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, fl
   const dim3 grid(BT * g * g + BT), block(256);
   if (dt == VCAP_DT_BF16)
     hipLaunchKernelGGL((vcap_patchify_kernel<bf16_t>), grid, block, 0, s, frames, (bf16_t*)patches, x, cls, pos, BT,
+                       img, p, Kp, N, D);
+  else if (dt == VCAP_DT_F16)
+    hipLaunchKernelGGL((vcap_patchify_kernel<f16_t>), grid, block, 0, s, frames, (f16_t*)patches, x, cls, pos, BT,
                        img, p, Kp, N, D);
   else
     hipLaunchKernelGGL((vcap_patchify_kernel<float>), grid, block, 0, s, frames, (float*)patches, x, cls, pos, BT,
@@ -113,6 +119,10 @@ hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, fl
 constexpr int HEAD_OUT = 16;    // proj outputs per head block (4 per wave)
 constexpr int PREFIX_OUT = 64;  // mapper outputs per prefix block (16 per wave, 4 at a time)
 
+// H16 (f16 operands): encoder.proj runs inside the autocast block (video_encoder.py:301-324), so the
+// pooled row and the proj weights are rounded to fp16 on the way in and the output on the way out;
+// the final LayerNorm and the temporal mean stay f32 (autocast's layer_norm returns f32).
+template <bool H16>
 __global__ __launch_bounds__(256) void vcap_vit_head_kernel(const float* __restrict__ x, int T, int N, int D,
                                                             const float* __restrict__ ng, const float* __restrict__ nb,
                                                             float neps, const float* __restrict__ pw,
@@ -153,7 +163,10 @@ __global__ __launch_bounds__(256) void vcap_vit_head_kernel(const float* __restr
     if (c < D) part[wave][c] = accv[i];
   }
   __syncthreads();
-  for (int c = tid; c < D; c += 256) pooled[c] = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)T;
+  for (int c = tid; c < D; c += 256) {
+    const float pv = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)T;
+    pooled[c] = H16 ? Autocast<f16_t>::rnd(pv) : pv;
+  }
   __syncthreads();
   // 2) encoder.proj, 4 outputs per wave with all their weight loads in flight
   const int ob = blockIdx.y * HEAD_OUT + wave * 4;
@@ -170,13 +183,13 @@ __global__ __launch_bounds__(256) void vcap_vit_head_kernel(const float* __restr
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int c = c0 + lane + 64 * i;
-        if (c < D) sacc[k] += pooled[c] * wv[k][i];
+        if (c < D) sacc[k] += pooled[c] * (H16 ? Autocast<f16_t>::rnd(wv[k][i]) : wv[k][i]);
       }
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float v = wave_sum(sacc[k]);
-    if (lane == 0 && ob + k < VD) emb[(long)b * VD + ob + k] = v + pb[ob + k];
+    if (lane == 0 && ob + k < VD) emb[(long)b * VD + ob + k] = H16 ? Autocast<f16_t>::rnd(v + pb[ob + k]) : v + pb[ob + k];
   }
 }
 
@@ -250,14 +263,18 @@ __global__ __launch_bounds__(256) void vcap_prefix_map_kernel(const float* __res
 hipError_t vcap_vit_head_prefix_dispatch(const float* x, int B, int T, int N, int D, const float* ng, const float* nb,
                                          float neps, const float* pw, const float* pb, int VD, float ln_scale,
                                          float in_weight, const float* mw, const float* mb, int MO, float* enc_out,
-                                         float* prefix, const float* emb_in, float* emb_scratch, hipStream_t s) {
+                                         float* prefix, const float* emb_in, float* emb_scratch, hipStream_t s,
+                                         int f16_head) {
   if (D > 1024 || VD > 1024 || B <= 0) return hipErrorInvalidValue;
   const float* emb = emb_in;
   if (x) {
     float* e = enc_out ? enc_out : emb_scratch;
     if (!e) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(vcap_vit_head_kernel, dim3(B, (VD + HEAD_OUT - 1) / HEAD_OUT), dim3(256), 0, s, x, T, N, D, ng,
-                       nb, neps, pw, pb, VD, e);
+    const dim3 hgrid(B, (VD + HEAD_OUT - 1) / HEAD_OUT);
+    if (f16_head)
+      hipLaunchKernelGGL(vcap_vit_head_kernel<true>, hgrid, dim3(256), 0, s, x, T, N, D, ng, nb, neps, pw, pb, VD, e);
+    else
+      hipLaunchKernelGGL(vcap_vit_head_kernel<false>, hgrid, dim3(256), 0, s, x, T, N, D, ng, nb, neps, pw, pb, VD, e);
     if (hipError_t err = hipGetLastError()) return err;
     emb = e;
   }
@@ -291,6 +308,9 @@ hipError_t vcap_vit_pool_dispatch(int dt, const void* x, void* y, int B, int T, 
   const dim3 grid((B * C + 255) / 256), block(256);
   if (dt == VCAP_DT_BF16)
     hipLaunchKernelGGL((vcap_vit_pool_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)x, (bf16_t*)y, B, T, tokens,
+                       C, gap);
+  else if (dt == VCAP_DT_F16)
+    hipLaunchKernelGGL((vcap_vit_pool_kernel<f16_t>), grid, block, 0, s, (const f16_t*)x, (f16_t*)y, B, T, tokens,
                        C, gap);
   else
     hipLaunchKernelGGL((vcap_vit_pool_kernel<float>), grid, block, 0, s, (const float*)x, (float*)y, B, T, tokens, C,

@@ -185,8 +185,8 @@ class HipTextDecoder:
 
 def resolve_decoder_precision(precision: str, decoder_precision: str = "auto") -> str:
     """The GPT-2 decoder's arithmetic.  "auto" = fp32 whatever the ViT runs in: the reference's own
-    split - its ViT under half-precision autocast (src/models/video_encoder.py:261-264,
-    backend_config.py:46), its decoder always fp32 (src/models/text_decoder.py:131-144) - so the
+    split - its ViT under fp16 autocast (src/models/video_encoder.py:261-264, backend_config.py:46;
+    ViT precision "fp16" here, "bf16" being this project's throughput choice), its decoder always fp32 (src/models/text_decoder.py:131-144) - so the
     drop-in surface decodes token-exactly by default.  "bf16" is the throughput mode (BASELINE
     configs[1] line of bench.py)."""
     if decoder_precision == "auto":
@@ -200,7 +200,8 @@ class HipVideoCaptionModel:
     def __init__(self, sd, vit_name: str = "vit_base_patch16_224", gpt2_name: str = "gpt2", prefix_len: int = 4,
                  precision: str = "bf16", device="cuda", tokenizer_dir: str = "", use_graph: bool = True,
                  decoder_precision: str = "auto"):
-        """precision: the ViT's operand type (bf16 / fp32 / fp8 = MXFP8 block GEMMs); decoder_precision:
+        """precision: the ViT's operand type (bf16 / fp16 = the reference's autocast dtype / fp32 / fp8 =
+        MXFP8 block GEMMs); decoder_precision:
         see resolve_decoder_precision (default fp32, the reference's decoder arithmetic)."""
         self.device = torch.device(device)
         self.vit_arch, self.gpt2_arch = configs.vit_arch(vit_name), configs.gpt2_arch(gpt2_name)

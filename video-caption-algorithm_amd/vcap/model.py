@@ -1,7 +1,7 @@
 """Device-resident ViT encoder and GPT-2 decoder driven through the C ABI.
 
 `HipViTEncoder` and `HipGPT2Decoder` own the packed weights in HBM (operand dtype bf16 for
-throughput or fp32 for the parity mode), build the include/vcap.h descriptors once, keep a
+throughput or fp32 for the parity mode; the ViT also fp16, the reference's autocast dtype, and MXFP8), build the include/vcap.h descriptors once, keep a
 reusable workspace, and issue one ABI call per encode / per whole decode.
 
 Weight packing from the reference's state-dict layout:
@@ -26,7 +26,10 @@ from .configs import VIDEO_DIM, GPT2Arch, ViTArch
 _DTYPES = {"bf16": (N.DT_BF16, torch.bfloat16), "fp32": (N.DT_F32, torch.float32)}
 # ViT only: "fp8" = MXFP8 block GEMMs (QKV / attn-proj / fc1 / fc2: e4m3 + E8M0 per 32 K elements,
 # the gfx950 scaled-MFMA format; BASELINE configs[4]); patch-embed and QK^T / PV run in bf16.
-_VIT_DTYPES = dict(_DTYPES, fp8=(N.DT_MXFP8, torch.bfloat16))
+# "fp16" = the reference's own ViT precision (torch.autocast(dtype=float16), video_encoder.py:261-264):
+# fp16 operands at the bf16 MFMA rate, rounded where autocast rounds.  The decoder has no fp16 mode
+# (the reference keeps GPT-2 in fp32).
+_VIT_DTYPES = dict(_DTYPES, fp8=(N.DT_MXFP8, torch.bfloat16), fp16=(N.DT_F16, torch.float16))
 
 
 def _dtype(mode: str):
@@ -92,9 +95,9 @@ class HipViTEncoder:
                                              _stream(dev)), "vcap_mx_quantize")
             return q, sc
 
-        kstep = 32 if self.dt == N.DT_F32 else 64
+        kstep = 128 // tdt.itemsize   # one 128-byte K-tile row of the patch-embed operand dtype
         K = arch.patch_k
-        self.kpad = ((K + 63) // 64) * 64 if kstep == 64 else ((K + 31) // 32) * 32
+        self.kpad = ((K + kstep - 1) // kstep) * kstep
         pw = torch.zeros(arch.dim, self.kpad, dtype=torch.float32)
         pw[:, :K] = torch.from_numpy(np.ascontiguousarray(sd[p + "patch_embed.proj.weight"])).reshape(arch.dim, K)
         self._keep: List[torch.Tensor] = []
