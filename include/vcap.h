@@ -106,6 +106,11 @@ typedef struct vcap_gpt2_layer {
   const void* mproj_w; const float* mproj_b; /* packed [E, 4E] */
 } vcap_gpt2_layer;
 
+/* Widths: n_embd any multiple of 128 up to 1024 with n_head = n_embd / 64, in both dtypes.  The mlp
+ * c_proj (K = 4 * n_embd) splits its K range over workgroups only where a kernel implements it: bf16
+ * at K = 3072; f32 at K / 64 = 48 or 64 slabs (K = 3072 / 4096) with one 16-column tile per workgroup.
+ * Every other width and grid cap runs that projection unsplit (csrc/decode.hip
+ * vcap_rows_gemm_dispatch; DESIGN.md "Decoder widths"). */
 typedef struct vcap_gpt2_desc {
   int dtype;
   int n_embd, n_layer, n_head, vocab, n_positions, prefix_len;

@@ -157,3 +157,68 @@ def test_screen_bound_covers_adversarial_near_tie(device, sd, ga, mode):
         # both tokens in the history by step 2: the near-tie is between penalised negative scores
         assert set(f[0, :2].tolist()) == {a_id, b_id}, f[0]
         assert f[0, 2] in (a_id, b_id)
+
+
+# ---------------------------------------------------------------------------------------------------
+# The finalize kernel's multi-pass path: more survivors than one pass holds.  A screen whose bound
+# rules nothing out (SCREEN_C = 1e3) keeps every token of a 6001-token vocabulary: more than 64
+# candidate blocks (every block is rescanned), 3 passes of 2048 columns, a pass that adds to s_cv
+# without rescoring (2048 survivors = CAP - PASS, the next pass may still fit), a rescoring of a full
+# s_cv (4096) and one of the partial last pass (vocab not a multiple of 16).  The token must still be
+# the exact f32 argmax.  The default screen never leaves more than a handful of survivors, so no other
+# test has the survivor count above CAP - PASS.
+
+class _KeepsEverything(HipGPT2Decoder):
+    SCREEN_C = 1e3   # threshold far below every finite score: every token survives every pass
+
+
+def _small_vocab(E):
+    ga = configs.GPT2Arch(f"screen_{E}", E, 2, E // 64, vocab=6001, n_positions=64, bos_token_id=6000,
+                          eos_token_id=6000)
+    return ga, weights.synthetic_gpt2(4, ga)
+
+
+@pytest.fixture(scope="module")
+def many(device):
+    made = {}
+
+    def get(E):
+        if E not in made:
+            ga, sd6 = _small_vocab(E)
+            made[E] = (ga, sd6, HipGPT2Decoder(sd6, ga, "fp32", device, screen=False),
+                       HipGPT2Decoder(sd6, ga, "fp32", device), _KeepsEverything(sd6, ga, "fp32", device))
+        return made[E]
+    return get
+
+
+@pytest.mark.parametrize("E,B", [(768, 1), (768, 16), (1024, 1)])
+def test_screen_with_every_token_surviving(device, many, E, B):
+    ga, _, full, scr, keep = many(E)
+    assert not full.screen and scr.screen and keep.screen
+    pre = _prefix(device, B, ga, 300 + B)
+    for name, cfg in _cfgs(ga, 0).items():
+        a, b, c = _ids(full, pre, ga, cfg), _ids(scr, pre, ga, cfg), _ids(keep, pre, ga, cfg)
+        c2 = _ids(keep, pre, ga, cfg)      # the captured graph replayed
+        assert np.array_equal(a, b), (name, a, b)
+        assert np.array_equal(a, c), (name, a, c)
+        assert np.array_equal(c, c2), name
+
+
+def test_every_token_surviving_ties_take_the_lowest_id(device, many):
+    """test_screen_ties_take_the_lowest_id with all 6001 tokens rescored: the 41 tied copies of the
+    winner's row reach the rescoring in different passes' order, and the lowest id still wins."""
+    ga, sd6, full0, _, _ = many(768)
+    pre = _prefix(device, 4, ga, 7)
+    cfg = _cfgs(ga, 0)["hf"]
+    t0 = int(_ids(full0, pre, ga, cfg)[0, 0])
+    lo = t0 if t0 + 41 <= ga.vocab - 1 else t0 - 40      # clear of eos (banned until min_new_tokens)
+    sd2 = dict(sd6)
+    wte = np.array(sd6[WTE], dtype=np.float32, copy=True)
+    wte[lo: lo + 41] = wte[t0]
+    sd2[WTE] = wte
+    sd2["decoder.model.lm_head.weight"] = wte
+    keep = _KeepsEverything(sd2, ga, "fp32", device)
+    full = HipGPT2Decoder(sd2, ga, "fp32", device, screen=False)
+    a, b = _ids(keep, pre, ga, cfg), _ids(full, pre, ga, cfg)
+    assert np.array_equal(a, b), (a, b)
+    assert a[0, 0] == lo   # the tie went to the lowest id

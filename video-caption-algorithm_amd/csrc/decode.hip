@@ -382,8 +382,9 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
   // and every stored output are those of the full-tile workgroup
   // a.sk_part (the bf16 mlp c_proj, r06): K split over a workgroup pair per 16-column tile and 16-row
   // chunk, each workgroup one K half of the whole tile - half the activation rows per workgroup, the
-  // pair meeting as in vcap_rows_gemv8_kernel<float, NSL, 2, 1>
-  constexpr bool CAN_SPLIT = EPI == EPI_RESID && NTB == 1 && MT == 1 && PRO == PRO_DIRECT;
+  // pair meeting as in vcap_rows_gemv8_kernel<float, NSL, 2, 1>.  bf16 only: an f32 launch of this
+  // kernel never splits, whatever a.sk_part holds (the f32 split is vcap_rows_gemv8_kernel's)
+  constexpr bool CAN_SPLIT = sizeof(T) == 2 && EPI == EPI_RESID && NTB == 1 && MT == 1 && PRO == PRO_DIRECT;
   const bool split = CAN_SPLIT && a.sk_part != nullptr;
   const bool half = EPI == EPI_RESID && NTB == 1 && a.half && !split;
   const int hsel = half ? (int)(blockIdx.x & 1) : -1;
@@ -1184,6 +1185,10 @@ __global__ __launch_bounds__(256) void vcap_decode_finalize_kernel(
           __syncthreads();  // s_cv / s_ncv reused
           if (tid == 0) s_ncv = 0;
           __syncthreads();
+        } else {
+          // every wave has read s_ncv before any wave's next-pass atomicAdd moves it: ncv, and with
+          // it the branch above and rescore's barriers, is the same in all four waves
+          __syncthreads();
         }
       }
       __syncthreads();  // s_red reads done
@@ -1259,7 +1264,8 @@ static int allow_lds(Kern k, int& limit) {
 
 template <typename T, int MT, int NTB, int PRO, int EPI, int NSL>
 static hipError_t launch_gemv(const RowsGemmArgs& a, hipStream_t s) {
-  const int half = EPI == EPI_RESID && NTB == 1 && (a.half || a.sk_part) ? 2 : 1;
+  // the grid doubles for a.half and for the bf16 K split (the kernel's CAN_SPLIT), nothing else
+  const int half = EPI == EPI_RESID && NTB == 1 && (a.half || (sizeof(T) == 2 && a.sk_part)) ? 2 : 1;
   const dim3 grid(half * ((a.N + NTB * 16 - 1) / (NTB * 16)), (a.M + MT * 16 - 1) / (MT * 16));
   const size_t lds = PRO == PRO_LN ? (size_t)MT * 16 * a.K * sizeof(T) : 0;
   static int limit = 0;
@@ -1785,8 +1791,14 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
   // tile in bf16: its device beam search is priced against the reference's hypotheses under fp32
   // (test_l14_medium_beam4_bf16_priced_against_reference), and a beam search's path moves with any
   // change of bf16 summation order.)
-  if (dt == VCAP_DT_BF16 && ah.sk_part &&
-      !(pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && a.K == 3072)) {
+  // the f32 K split is vcap_rows_gemv8_kernel's alone: PRO_DIRECT + EPI_RESID, one tile per workgroup
+  // and K / 64 = 48 or 64 slabs (K = 3072 / 4096); every other f32 launch drops sk_part here, so
+  // the flag the runtime sets on each mlp c_proj never reaches a kernel or a grid that does not
+  // implement the split (n_embd = 256: K = 1024 is vcap_rows_gemv_kernel<float, .., 16>, whose
+  // CAN_SPLIT and launch_gemv's grid doubling are bf16-only for the same reason)
+  const bool bf16_split_ok = pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && a.K == 3072;
+  const bool f32_split_ok = pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && (a.K / 64 == 48 || a.K / 64 == 64);
+  if (ah.sk_part && !(dt == VCAP_DT_BF16 ? bf16_split_ok : f32_split_ok)) {
     ah.sk_part = nullptr;
     ah.sk_cnt = nullptr;
   }
