@@ -70,39 +70,43 @@ def patch_decode(s: str) -> str:
                         "  const unsigned long long t1 = VCAP_RT();\n"
                         "  asm volatile(\"\" :: \"v\"(wf[NSL - 1][NTB - 1].x));\n"
                         "  const unsigned long long tw = VCAP_RT();\n", 1)
-    body = body.replace("  if constexpr (EPI == EPI_LOGITS) toks.template mark<NTB>(a, m0, n0, s_rep, s_ban);\n  __syncthreads();\n",
-                        "  const unsigned long long t2 = VCAP_RT();\n  if constexpr (EPI == EPI_LOGITS) toks.template mark<NTB>(a, m0, n0, s_rep, s_ban);\n  __syncthreads();\n  const unsigned long long t3 = VCAP_RT();\n", 1)
+    mark = "  if constexpr (EPI == EPI_LOGITS) toks.mark(a, m0, n0, NTB * 16, &s_rep[0][0], &s_ban[0][0], NTB * 16);\n  __syncthreads();\n"
+    body = body.replace(mark, "  const unsigned long long t2 = VCAP_RT();\n" + mark + "  const unsigned long long t3 = VCAP_RT();\n", 1)
     body = body.replace("  rows_epilogue<T, MT, NTB, EPI>(a, m0, red, pre_bias, pre_res, lg, s_rep, s_ban, n0, hsel);\n}",
                         "  rows_epilogue<T, MT, NTB, EPI>(a, m0, red, pre_bias, pre_res, lg, s_rep, s_ban, n0, hsel);\n"
                         "  if (threadIdx.x == 0) vcap_stamp_rec((unsigned long long)((NSL << 12) | (EPI << 8) | (PRO << 4) | NTB) | ((unsigned long long)MT << 20) | ((unsigned long long)(hsel >= 0) << 24), t0, t1, tw, t2, t3, VCAP_RT());\n}", 1)
     assert body.count("VCAP_RT()") == 6, body.count("VCAP_RT()")
     s = s[:k0] + body + s[k1:]
-    # decode attention (c64): entry | every load landed | output stored (issued)
+    # decode attention (c64, both element types): entry | every load landed | output stored (issued)
     a0 = s.index("void vcap_decode_attention_c64_kernel(")
-    a1 = s.index("__global__ __launch_bounds__(64) void vcap_decode_attention_c64f_kernel", a0)
+    a1 = s.index("hipError_t vcap_decode_attention_dispatch(", a0)
     att = s[a0:a1]
     att = att.replace("  __shared__ float s_p[64];\n", "  __shared__ float s_p[64];\n  const unsigned long long t0 = VCAP_RT();\n", 1)
-    att = att.replace("  c64_issue(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n",
-                      "  c64_issue(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n  asm volatile(\"\" :: \"v\"(L.vv[7].x));\n"
+    att = att.replace("  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n",
+                      "  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n"
+                      "  asm volatile(\"\" :: \"v\"(L.vv[7][C64Loads<T>::NV - 1].x));\n"
                       "  const unsigned long long t1 = VCAP_RT();\n", 1)
     att = att[:att.rindex("}")] + "  if (threadIdx.x == 0) vcap_stamp_rec(0xA000ull, t0, t1, t1, t1, t1, VCAP_RT());\n}\n\n"
     assert att.count("VCAP_RT()") == 3, att.count("VCAP_RT()")
     s = s[:a0] + att + s[a1:]
-    # lm_head stream kernel (greedy / screen): entry | ln_f tile in LDS (+ flags) | first column group
-    # done | second group done | last group done | argmax partials written  (tag 0xC000)
-    l0 = s.index("__global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a, int tpw) {")
-    l1 = s.index("template <typename T, int NSL>\nstatic bool launch_lm_stream", l0)
+    # lm_head stream kernel (greedy / screen): entry | ln_f tile in LDS (+ flags zeroed) | first column
+    # group done | second group done | last group done | argmax partials written  (tag 0xC000).  The
+    # stamps sit in the walker it shares with the beam search's LSE kernel; only the greedy sink records.
+    s = s.replace("#include <algorithm>\n", "#include <algorithm>\n#include <type_traits>\nstruct LmArgmaxSink;\n", 1)
+    l0 = s.index("VCAP_DEV void lm_head_walk(")
+    l1 = s.index("// Greedy sink:", l0)
     lm = s[l0:l1]
     lm = lm.replace("  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;\n",
                     "  const unsigned long long st0 = VCAP_RT();\n  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;\n", 1)
-    lm = lm.replace("  __syncthreads();  // flags zeroed, A tile written\n",
-                    "  __syncthreads();  // flags zeroed, A tile written\n  const unsigned long long st1 = VCAP_RT();\n"
+    lm = lm.replace("  __syncthreads();  // A tile written\n",
+                    "  __syncthreads();  // A tile written\n  const unsigned long long st1 = VCAP_RT();\n"
                     "  unsigned long long st2 = 0, st3 = 0;\n", 1)
     lm = lm.replace("    group(wA, gi);\n", "    group(wA, gi);\n    if (gi == 0) st2 = VCAP_RT();\n", 1)
     lm = lm.replace("      group(wB, gi + 1);\n", "      group(wB, gi + 1);\n      if (gi == 0) st3 = VCAP_RT();\n", 1)
-    lm = lm.replace("  argmax_take(bv_run, bi_run, dpp_f<DPP_XOR1>(bv_run), dpp_i<DPP_XOR1>(bi_run));\n",
-                    "  const unsigned long long st4 = VCAP_RT();\n  argmax_take(bv_run, bi_run, dpp_f<DPP_XOR1>(bv_run), dpp_i<DPP_XOR1>(bi_run));\n", 1)
-    lm = lm[:lm.rindex("}")] + "  if (threadIdx.x == 0) vcap_stamp_rec(0xC000ull, st0, st1, st2, st3 ? st3 : st2, st4, VCAP_RT());\n}\n\n"
+    fin = "#pragma unroll\n  for (int i = 0; i < MT; ++i) sink.finish(a, i, i * 16 + row, col);\n"
+    lm = lm.replace(fin, "  const unsigned long long st4 = VCAP_RT();\n" + fin, 1)
+    lm = lm[:lm.rindex("}")] + ("  if (std::is_same<Sink, LmArgmaxSink>::value && threadIdx.x == 0)\n"
+                                "    vcap_stamp_rec(0xC000ull, st0, st1, st2, st3 ? st3 : st2, st4, VCAP_RT());\n}\n\n")
     assert lm.count("VCAP_RT()") == 6, lm.count("VCAP_RT()")
     s = s[:l0] + lm + s[l1:]
     return s
@@ -111,7 +115,7 @@ def patch_decode(s: str) -> str:
 def patch_attention(s: str) -> str:
     s = s.replace('#include "vcap_kernels.h"\n', '#include "vcap_kernels.h"\n' + header("_attn"), 1)
     k0 = s.index("void vcap_vit_attention_bf16_kernel(")
-    ends = [s.find(m, k0) for m in ("// Persistent walk over", "template <int KT, int KE, int WAVES, bool MXO>\nstatic hipError_t launch_attn_bf16")]
+    ends = [s.find(m, k0) for m in ("// Persistent walk over", "template <int KT, int KE, int WAVES, bool MXO, typename T>\nstatic hipError_t launch_attn_bf16")]
     k1 = min(e for e in ends if e > 0)
     b = s[k0:k1]
     b = b.replace("  const int fr = lane & 15, fg = lane >> 4;\n", "  const int fr = lane & 15, fg = lane >> 4;\n  const unsigned long long t0 = VCAP_RT();\n", 1)

@@ -70,6 +70,73 @@ VCAP_DEV const u32x4* packed_frag(const void* w, int tile, int nslab, int slab, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Epilogue inputs of one output element (row m, column n; clamped, selected later): bias, and the
+// residual when RES.  Never a guarded load: the bias load is unconditional (from a valid address
+// when there is no bias) and a select follows - a load guarded by the runtime `a.bias` test compiled
+// to a branch + vmcnt(0) that waited for the whole weight stream before the LayerNorm / A-fragment
+// work could start.
+template <bool RES>
+VCAP_DEV void epi_inputs(const RowsGemmArgs& a, int m, int n, float& bias, float& res) {
+  const int mc = min(m, a.M - 1), nc = min(n, a.N - 1);
+  const float bl = *(a.bias ? a.bias + nc : (const float*)a.x);
+  bias = a.bias ? bl : 0.f;
+  res = 0.f;
+  if constexpr (RES) res = ((const float*)a.out)[(long)mc * a.ldo + nc];
+}
+
+// The logits processors of one element, in HF's order: RepetitionPenalty -> NoRepeatNGram ->
+// MinNewTokens.  rep / ban: token n is in the row's history / ban list (ProcToks flags).
+VCAP_DEV float apply_processors(const RowsGemmArgs& a, float v, bool rep, bool ban, int n) {
+  float sv = v;
+  if (rep) sv = sv < 0.f ? sv * a.rep_penalty : sv / a.rep_penalty;
+  if (ban) sv = -INFINITY;
+  if (n == a.eos && a.gen_len < a.min_new) sv = -INFINITY;
+  return sv;
+}
+
+// One f32 row -> LayerNorm -> row `ml` of the XOR-swizzled LDS A tile (rows of K elements of T, the
+// 16-byte chunk index xor (ml & 15); trow = tile + ml * K * sizeof(T), the row's base, worked out by
+// the caller), the ONE LayerNorm of the decode kernels.  x[c] / gv[c] / bv[c]
+// hold features [c * 256 + lane * 4, +4) of the row and of the affine; chunks past K (clamped loads)
+// take no part - the guard folds away where K is a compile-time constant, and a caller whose K is
+// KC * 256 by construction but not a constant drops it (GUARD = false).  Sums as
+// (x + y) + (z + w) per chunk, chunks in order, then the wave; sumsq4 and ln_affine4 as written in
+// vcap_common.h.  A dead row (!live: past M) stores zeros.  copy_row: optional f32 copy of the
+// normalised row (the lm_head screen's screen_h).
+template <typename T, int KC, bool GUARD = true>
+VCAP_DEV void ln_row_to_tile(const f32x4 (&x)[KC], const f32x4 (&gv)[KC], const f32x4 (&bv)[KC], int K, float eps,
+                             bool live, int ml, char* trow, float* copy_row = nullptr) {
+  const int lane = threadIdx.x & 63;
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < KC; ++c)
+    if (!GUARD || c * 256 + lane * 4 < K) s += (x[c].x + x[c].y) + (x[c].z + x[c].w);
+  const float mean = wave_sum(s) / (float)K;
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < KC; ++c)
+    if (!GUARD || c * 256 + lane * 4 < K) {
+      const f32x4 d = x[c] - mean;
+      ss += sumsq4(d);
+    }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)K + eps);
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    if (!GUARD || c * 256 + lane * 4 < K) {
+      const f32x4 y = live ? ln_affine4(x[c], mean, rstd, gv[c], bv[c]) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (copy_row && live) *reinterpret_cast<f32x4*>(copy_row + c * 256 + lane * 4) = y;
+      const int byte = (c * 256 + lane * 4) * (int)sizeof(T);
+      char* dst = trow + ((((byte >> 4) ^ (ml & 15))) << 4) + (byte & 15);
+      if constexpr (sizeof(T) == 2) {
+        *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf2(y.x, y.y), pack_bf2(y.z, y.w)};
+      } else {
+        *reinterpret_cast<f32x4*>(dst) = y;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Shared epilogue of the rows kernels: split-K partial tiles (red[wave]) -> role output.
 // pre_bias/pre_res were loaded at kernel start; s_rep/s_ban flag the processors' tokens that fall
 // in this workgroup's column range.
@@ -115,15 +182,12 @@ VCAP_DEV void rows_epilogue(const RowsGemmArgs& a, int m0, const float (*red)[MT
         if (n < N) a.logits_raw[(long)m * N + n] = v;
         lg[ml][j * 16 + col] = n < N ? v : -INFINITY;
       }
-    } else {  // EPI_LOGITS: RepetitionPenalty -> NoRepeatNGram -> MinNewTokens (HF processor order)
+    } else {  // EPI_LOGITS
       if (m < M) {
         float sv = -INFINITY;
         if (n < N) {
           if (a.logits_raw) a.logits_raw[(long)m * N + n] = v;
-          sv = v;
-          if (s_rep[ml][j * 16 + col]) sv = sv < 0.f ? sv * a.rep_penalty : sv / a.rep_penalty;
-          if (s_ban[ml][j * 16 + col]) sv = -INFINITY;
-          if (n == a.eos && a.gen_len < a.min_new) sv = -INFINITY;
+          sv = apply_processors(a, v, s_rep[ml][j * 16 + col], s_ban[ml][j * 16 + col], n);
           if (a.proc_out) a.proc_out[(long)m * N + n] = sv;
         }
         lg[ml][j * 16 + col] = sv;
@@ -184,17 +248,17 @@ struct ProcToks {
       nb[q] = a.nbanned[m];
     }
   }
-  template <int NTB>
-  VCAP_DEV void mark(const RowsGemmArgs& a, int m0, int n0, unsigned char (*s_rep)[NTB * 16],
-                     unsigned char (*s_ban)[NTB * 16]) const {
+  // flags of the workgroup's column window [c_begin, c_begin + ncols); flag rows are `ld` bytes apart
+  VCAP_DEV void mark(const RowsGemmArgs& a, int m0, int c_begin, int ncols, unsigned char* s_rep,
+                     unsigned char* s_ban, int ld) const {
 #pragma unroll
     for (int q = 0; q < MT * 4; ++q) {
       const int i = threadIdx.x + q * 256;
       const int m = i >> 6, t = i & 63;  // m: row within the chunk
       if (m0 + m >= a.M) continue;
-      const unsigned hc = (unsigned)(h[q] - n0), bc = (unsigned)(b[q] - n0);
-      if (a.rep_penalty != 1.0f && t < a.gen_len && hc < (unsigned)(NTB * 16)) s_rep[m][hc] = 1;
-      if (t < nb[q] && bc < (unsigned)(NTB * 16)) s_ban[m][bc] = 1;
+      const unsigned hc = (unsigned)(h[q] - c_begin), bc = (unsigned)(b[q] - c_begin);
+      if (a.rep_penalty != 1.0f && t < a.gen_len && hc < (unsigned)ncols) s_rep[m * ld + hc] = 1;
+      if (t < nb[q] && bc < (unsigned)ncols) s_ban[m * ld + bc] = 1;
     }
   }
 };
@@ -213,113 +277,83 @@ constexpr bool gemv_stream_a() {
 // P.V with lane = (key group kg of 8, 8 consecutive dims d8), partial sums reduced over the 8 key
 // groups by DPP + permlane swaps.  c64_issue issues every load of the item at once (q, the lane's
 // K row, its 8 V rows: one memory round trip); c64_finish is the arithmetic, the ONE operation
-// order of vcap_decode_attention_c64_kernel.
+// order of vcap_decode_attention_c64_kernel: the score sums dims 0..63 in order, and the P.V sums run
+// over the same key groups and reduction as vcap_decode_attention_kernel<T>.
+template <typename T>
 struct C64Loads {
-  u32x4 q;      // 8 of the head's 64 query dims: chunk (lane & 7)
-  u32x4 kv[8];  // K row of key min(lane, ctx - 1)
-  u32x4 vv[8];  // V rows of keys it * 8 + kg (clamped), dims [d8, d8 + 8)
+  static constexpr int E8 = Frag<T>::kElems, NK = 64 / E8, NV = 8 / E8;  // bf16: 8, 8, 1; f32: 4, 16, 2
+  u32x4 q;          // E8 of the head's 64 query dims: chunk (lane & (NK - 1))
+  u32x4 kv[NK];     // K row of key min(lane, ctx - 1)
+  u32x4 vv[8][NV];  // V rows of keys it * 8 + kg (clamped), dims [d8, d8 + 8)
 };
 
-VCAP_DEV u32x4 c64_ld16(const bf16_t* base, long elem) { return *reinterpret_cast<const u32x4*>(base + elem); }
-
-VCAP_DEV void c64_issue(C64Loads& L, const bf16_t* q, const bf16_t* kc, const bf16_t* vc, int maxp, int m, int h,
-                        int H, int seq, int ctx) {
-  const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
-  auto row_of = [&](int j) { return (((long)(seq * maxp + (j >> 4)) * H + h) * 16 + (j & 15)) * 64; };
-  L.q = c64_ld16(q, (long)m * H * 64 + h * 64 + (lane & 7) * 8);
-  const long kr = row_of(min(lane, ctx - 1));
+// the E8 elements of a 16-byte chunk as floats, in memory order
+template <typename T>
+VCAP_DEV void chunk_to_f(const u32x4& v, float (&f)[Frag<T>::kElems]) {
+  if constexpr (sizeof(T) == 2) {
+    const unsigned w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-  for (int c = 0; c < 8; ++c) L.kv[c] = c64_ld16(kc, kr + c * 8);
+    for (int e = 0; e < 4; ++e) {
+      f[2 * e] = bf2f((bf16_t)(w4[e] & 0xffff));
+      f[2 * e + 1] = bf2f((bf16_t)(w4[e] >> 16));
+    }
+  } else {
+    const f32x4 v4 = __builtin_bit_cast(f32x4, v);
 #pragma unroll
-  for (int it = 0; it < 8; ++it) L.vv[it] = c64_ld16(vc, row_of(min(it * 8 + kg, ctx - 1)) + d8);
+    for (int e = 0; e < 4; ++e) f[e] = v4[e];
+  }
 }
 
-// s_q / s_p: this wave's 64 floats each of LDS; orow = out + m * E + h * 64
-VCAP_DEV void c64_finish(const C64Loads& L, float* s_q, float* s_p, int ctx, bf16_t* orow) {
-  const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
-  if (lane < 8) {
-    const unsigned w4[4] = {L.q.x, L.q.y, L.q.z, L.q.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s_q[lane * 8 + 2 * e] = bf2f((bf16_t)(w4[e] & 0xffff));
-      s_q[lane * 8 + 2 * e + 1] = bf2f((bf16_t)(w4[e] >> 16));
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  float sc = 0.f;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const bf16_t* ke = reinterpret_cast<const bf16_t*>(&L.kv[c]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sc += s_q[c * 8 + e] * bf2f(ke[e]);
-  }
-  sc *= 0.125f;
-  const bool live = lane < ctx;
-  const float mx = wave_max(live ? sc : -INFINITY);
-  const float p = live ? __expf(sc - mx) : 0.f;
-  const float sum = wave_sum(p);
-  s_p[lane] = p;
-  __builtin_amdgcn_wave_barrier();
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const int jj = it * 8 + kg;
-    const float pj = jj < ctx ? s_p[jj] : 0.f;
-    const unsigned w4[4] = {L.vv[it].x, L.vv[it].y, L.vv[it].z, L.vv[it].w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      o[2 * e] += pj * bf2f((bf16_t)(w4[e] & 0xffff));
-      o[2 * e + 1] += pj * bf2f((bf16_t)(w4[e] >> 16));
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = rows_sum(o[e] + dpp_f<0x128>(o[e]));
-  if (kg == 0) {
-    const float inv = 1.0f / sum;
-    *reinterpret_cast<u32x4*>(orow + d8) =
+// 8 consecutive output dims o[] * inv -> orow (16-byte aligned)
+template <typename T>
+VCAP_DEV void store_out8(T* orow, const float (&o)[8], float inv) {
+  if constexpr (sizeof(T) == 2) {
+    *reinterpret_cast<u32x4*>(orow) =
         (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv),
                 pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
+  } else {
+    *reinterpret_cast<f32x4*>(orow) = (f32x4){o[0], o[1], o[2], o[3]} * inv;
+    *reinterpret_cast<f32x4*>(orow + 4) = (f32x4){o[4], o[5], o[6], o[7]} * inv;
   }
 }
 
-// The f32 form (the f32 decoders): the same item on one wave with every load issued at once; the
-// score sums dims 0..63 in order and the P.V sums run over the same key groups and DPP / permlane
-// reduction as vcap_decode_attention_kernel<float>.
-struct C64LoadsF {
-  u32x4 q;       // 4 of the head's 64 query dims: chunk (lane & 15)
-  u32x4 kv[16];  // K row of key min(lane, ctx - 1)
-  u32x4 vv[8][2];  // V rows of keys it * 8 + kg (clamped), dims [d8, d8 + 8)
-};
-
-VCAP_DEV void c64f_issue(C64LoadsF& L, const float* q, const float* kc, const float* vc, int maxp, int m, int h,
-                         int H, int seq, int ctx) {
+template <typename T>
+VCAP_DEV void c64_issue(C64Loads<T>& L, const T* q, const T* kc, const T* vc, int maxp, int m, int h, int H, int seq,
+                        int ctx) {
+  constexpr int E8 = C64Loads<T>::E8, NK = C64Loads<T>::NK, NV = C64Loads<T>::NV;
   const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
   auto row_of = [&](int j) { return (((long)(seq * maxp + (j >> 4)) * H + h) * 16 + (j & 15)) * 64; };
-  auto ld = [](const float* base, long elem) { return *reinterpret_cast<const u32x4*>(base + elem); };
-  L.q = ld(q, (long)m * H * 64 + h * 64 + (lane & 15) * 4);
+  auto ld = [](const T* base, long elem) { return *reinterpret_cast<const u32x4*>(base + elem); };
+  L.q = ld(q, (long)m * H * 64 + h * 64 + (lane & (NK - 1)) * E8);
   const long kr = row_of(min(lane, ctx - 1));
 #pragma unroll
-  for (int c = 0; c < 16; ++c) L.kv[c] = ld(kc, kr + c * 4);
+  for (int c = 0; c < NK; ++c) L.kv[c] = ld(kc, kr + c * E8);
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const long vr = row_of(min(it * 8 + kg, ctx - 1)) + d8;
-    L.vv[it][0] = ld(vc, vr);
-    L.vv[it][1] = ld(vc, vr + 4);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) L.vv[it][v] = ld(vc, vr + v * E8);
   }
 }
 
-VCAP_DEV void c64f_finish(const C64LoadsF& L, float* s_q, float* s_p, int ctx, float* orow) {
+// s_q / s_p: this wave's 64 floats each of LDS (s_q 16-byte aligned); orow = out + m * E + h * 64
+template <typename T>
+VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, T* orow) {
+  constexpr int E8 = C64Loads<T>::E8, NK = C64Loads<T>::NK, NV = C64Loads<T>::NV;
   const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
-  if (lane < 16) *reinterpret_cast<f32x4*>(s_q + lane * 4) = __builtin_bit_cast(f32x4, L.q);
+  float f[E8];
+  if (lane < NK) {
+    chunk_to_f<T>(L.q, f);
+#pragma unroll
+    for (int e = 0; e < E8; ++e) s_q[lane * E8 + e] = f[e];
+  }
   __builtin_amdgcn_wave_barrier();
   float sc = 0.f;
 #pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    const f32x4 k4 = __builtin_bit_cast(f32x4, L.kv[c]);
+  for (int c = 0; c < NK; ++c) {
+    chunk_to_f<T>(L.kv[c], f);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) sc += s_q[c * 4 + e] * k4[e];
+    for (int e = 0; e < E8; ++e) sc += s_q[c * E8 + e] * f[e];
   }
   sc *= 0.125f;
   const bool live = lane < ctx;
@@ -335,19 +369,61 @@ VCAP_DEV void c64f_finish(const C64LoadsF& L, float* s_q, float* s_p, int ctx, f
   for (int it = 0; it < 8; ++it) {
     const int jj = it * 8 + kg;
     const float pj = jj < ctx ? s_p[jj] : 0.f;
-    const f32x4 v0 = __builtin_bit_cast(f32x4, L.vv[it][0]), v1 = __builtin_bit_cast(f32x4, L.vv[it][1]);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      o[e] += pj * v0[e];
-      o[4 + e] += pj * v1[e];
+    for (int v = 0; v < NV; ++v) {
+      chunk_to_f<T>(L.vv[it][v], f);
+#pragma unroll
+      for (int e = 0; e < E8; ++e) o[v * E8 + e] += pj * f[e];
     }
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = rows_sum(o[e] + dpp_f<0x128>(o[e]));
-  if (kg == 0) {
-    const float inv = 1.0f / sum;
-    *reinterpret_cast<f32x4*>(orow + d8) = (f32x4){o[0], o[1], o[2], o[3]} * inv;
-    *reinterpret_cast<f32x4*>(orow + d8 + 4) = (f32x4){o[4], o[5], o[6], o[7]} * inv;
+  if (kg == 0) store_out8<T>(orow + d8, o, 1.0f / sum);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K split of the residual GEMVs (the mlp c_proj).  The host's rows_split_plan (beside the dispatcher)
+// is the one place that decides whether a launch splits and into what; a kernel splits when the
+// launch carries a.sk_part AND its instantiation can (rows_can_split: the compile-time guard, so an
+// instantiation without the hand-off code ignores the flag).
+template <typename T, int MT, int NTB, int PRO, int EPI>
+constexpr bool rows_can_split() {
+  return EPI == EPI_RESID && NTB == 1 && PRO == PRO_DIRECT && (sizeof(T) == 4 || MT == 1);
+}
+
+// How the KP K parts of column group g (NT 16-column tiles; element ei of NT * 256) meet: through
+// global memory in the MI355X guide's valid hand-off form (Guideline 16 R1): every partial store is
+// sc1 (agent-scope relaxed atomic store: write-through) and every storing wave drains (vmcnt(0))
+// before the workgroup barrier; then one lane takes a ticket (agent-scope atomic add on sk_cnt[g],
+// zeroed per decode by vcap_decode_init; it advances by KP per launch).  The group's last arriver
+// (ksplit_arrive returns true there, false in the others, which exit) loads the other parts' partials
+// with sc1 loads: ksplit_sum, called by the threads that own an in-range element.  No one waits (no
+// spin), and the sum is p0 + p1 (KP = 2) or (p0 + p1) + (p2 + p3) (KP = 4) whichever part arrives
+// last: deterministic.
+template <int KP, int NT>
+VCAP_DEV bool ksplit_arrive(const RowsGemmArgs& a, long g, int ksel, int ei, bool mine, float part) {
+  __shared__ int s_ticket;
+  if (mine)
+    __hip_atomic_store(a.sk_part + ((g * KP + ksel) * NT) * 256 + ei, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
+  __syncthreads();
+  if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(a.sk_cnt + g, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  return (s_ticket & (KP - 1)) == KP - 1;  // the last of the group
+}
+template <int KP, int NT>
+VCAP_DEV float ksplit_sum(const RowsGemmArgs& a, long g, int ksel, int ei, float part) {
+  auto other = [&](int k) {
+    return __hip_atomic_load(a.sk_part + ((g * KP + k) * NT) * 256 + ei, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  if constexpr (KP == 2) {  // one unguarded load of the other half
+    const float o = other(ksel ^ 1);
+    return ksel == 0 ? part + o : o + part;
+  } else {
+    float p[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) p[k] = k == ksel ? part : other(k);
+    return (p[0] + p[1]) + (p[2] + p[3]);
   }
 }
 
@@ -381,10 +457,9 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
   // so a K = 3072 projection spreads its weight stream over twice the CUs; the MFMAs, their order
   // and every stored output are those of the full-tile workgroup
   // a.sk_part (the bf16 mlp c_proj, r06): K split over a workgroup pair per 16-column tile and 16-row
-  // chunk, each workgroup one K half of the whole tile - half the activation rows per workgroup, the
-  // pair meeting as in vcap_rows_gemv8_kernel<float, NSL, 2, 1>.  bf16 only: an f32 launch of this
-  // kernel never splits, whatever a.sk_part holds (the f32 split is vcap_rows_gemv8_kernel's)
-  constexpr bool CAN_SPLIT = sizeof(T) == 2 && EPI == EPI_RESID && NTB == 1 && MT == 1 && PRO == PRO_DIRECT;
+  // chunk, each workgroup one K half of the whole tile - half the activation rows per workgroup
+  // (ksplit_arrive / ksplit_sum; bf16 only: the f32 split is vcap_rows_gemv8_kernel's)
+  constexpr bool CAN_SPLIT = sizeof(T) == 2 && rows_can_split<T, MT, NTB, PRO, EPI>();
   const bool split = CAN_SPLIT && a.sk_part != nullptr;
   const bool half = EPI == EPI_RESID && NTB == 1 && a.half && !split;
   const int hsel = half ? (int)(blockIdx.x & 1) : -1;
@@ -439,17 +514,9 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
   // ---- 3) epilogue inputs
   float pre_bias[NE], pre_res[NE];
 #pragma unroll
-  for (int q = 0; q < NE; ++q) {
-    const int m = m0 + (q / NTB) * 16 + (tid >> 4), n = n0 + (q % NTB) * 16 + (tid & 15);
-    const int mc = min(m, M - 1), nc = min(n, N - 1);
-    // unconditional load (from a valid address when there is no bias), then a select: a load
-    // guarded by the runtime `a.bias` test compiled to a branch + vmcnt(0) that waited for the
-    // whole weight stream before the LayerNorm / A-fragment work could start
-    const float bl = *(a.bias ? a.bias + nc : (const float*)a.x);
-    pre_bias[q] = a.bias ? bl : 0.f;
-    pre_res[q] = 0.f;
-    if constexpr (EPI == EPI_RESID) pre_res[q] = ((const float*)a.out)[(long)mc * a.ldo + nc];
-  }
+  for (int q = 0; q < NE; ++q)
+    epi_inputs<EPI == EPI_RESID>(a, m0 + (q / NTB) * 16 + (tid >> 4), n0 + (q % NTB) * 16 + (tid & 15), pre_bias[q],
+                                 pre_res[q]);
   ProcToks<EPI == EPI_LOGITS ? MT : 1> toks;
   if constexpr (EPI == EPI_LOGITS) toks.load(a, m0);
   // Issue order fence: every load above is issued before any of the work below.  The empty asm
@@ -468,8 +535,10 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
 
   // ---- LayerNorm in registers -> swizzled LDS tile (waits only for step 1's loads)
   if constexpr (PRO == PRO_LN) {
-    const int rowb = K * (int)sizeof(T);
 #pragma unroll
+    // ln_row_to_tile's arithmetic written out (K = KC * 256 here, so no guard): through the helper these
+    // kernels - the hottest of a decode step - compiled to a different schedule that measured 5 % slower
+    // (f32 c_attn / c_fc, profiles/decode_refactor_ab.txt); this copy keeps the parent's ISA
     for (int r = 0; r < RPW; ++r) {
       const int m = wave + 4 * r;  // row within the chunk
       float s = 0.f;
@@ -484,6 +553,7 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
       }
       const float rstd = rsqrtf(wave_sum(ss) / (float)K + a.ln_eps);
       const bool live = m0 + m < M;
+      const int rowb = K * (int)sizeof(T);
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         const f32x4 y = live ? ln_affine4(xv[r][c], mean, rstd, gv[c], bv[c]) : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -541,29 +611,16 @@ __global__ __launch_bounds__(256) void vcap_rows_gemv_kernel(RowsGemmArgs a) {
     for (int j = 0; j < NTB; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave][(i * NTB + j) * 256 + (fg * 4 + r) * 16 + fr] = acc[i][j][r];
-  if constexpr (EPI == EPI_LOGITS) toks.template mark<NTB>(a, m0, n0, s_rep, s_ban);
+  if constexpr (EPI == EPI_LOGITS) toks.mark(a, m0, n0, NTB * 16, &s_rep[0][0], &s_ban[0][0], NTB * 16);
   __syncthreads();
   if constexpr (CAN_SPLIT) {
     if (split) {
-      // the pair hand-off (MI355X guide Guideline 16 R1): sc1 partial stores drained by every storing
-      // wave before the barrier, one agent-scope ticket, the second arriver's sc1 loads; the sum is
-      // p(K half 0) + p(K half 1) in that order whichever workgroup arrives second
-      __shared__ int s_ticket;
       const long pair = (long)blockIdx.y * (gridDim.x >> 1) + (blockIdx.x >> 1);
       const float part = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-      __hip_atomic_store(a.sk_part + (pair * 2 + ksel) * 256 + tid, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) s_ticket = __hip_atomic_fetch_add(a.sk_cnt + pair, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if ((s_ticket & 1) == 0) return;
+      if (!ksplit_arrive<2, 1>(a, pair, ksel, tid, true, part)) return;
       const int m = m0 + (tid >> 4), n = n0 + (tid & 15);
-      if (m < M && n < N) {
-        const float other =
-            __hip_atomic_load(a.sk_part + (pair * 2 + (ksel ^ 1)) * 256 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float v = (ksel == 0 ? part + other : other + part) + pre_bias[0];
-        ((float*)a.out)[(long)m * a.ldo + n] = pre_res[0] + v;
-      }
+      if (m < M && n < N)
+        ((float*)a.out)[(long)m * a.ldo + n] = pre_res[0] + (ksplit_sum<2, 1>(a, pair, ksel, tid, part) + pre_bias[0]);
       return;
     }
   }
@@ -588,7 +645,6 @@ __global__ __launch_bounds__(512) void vcap_rows_gemv8_kernel(RowsGemmArgs a) {
   static_assert(NSL % AB == 0, "A batches tile the wave's slabs");
   static_assert(NT == 1 || (KP == 4 && NT == 2), "column-tile pairs only with the 4-way K split");
   __shared__ __attribute__((aligned(16))) float red[8][NT * 256];
-  __shared__ int s_ticket;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
   const int M = a.M, N = a.N;
@@ -599,7 +655,7 @@ __global__ __launch_bounds__(512) void vcap_rows_gemv8_kernel(RowsGemmArgs a) {
   // the group's columns, so each ingests 1/KP of the activation rows (the f32 mlp c_proj's 196 KiB of
   // activations per workgroup was twice its weight slice: profiles/r06_decode_stamps.txt).  KP = 2,
   // NT = 1: 98 KiB of activations + 98 KiB of weights per workgroup; KP = 4, NT = 2 (GPT-2 small, r06
-  // late): 49 + 98 KiB, the same workgroup count.  The K parts meet below.
+  // late): 49 + 98 KiB, the same workgroup count.  The K parts meet in ksplit_arrive / ksplit_sum.
   const bool half = !SPLIT && a.half != 0;
   const int hsel = half ? (int)(blockIdx.x & 1) : -1;
   const int ksel = SPLIT ? (int)(blockIdx.x % KP) : 0;
@@ -628,10 +684,8 @@ __global__ __launch_bounds__(512) void vcap_rows_gemv8_kernel(RowsGemmArgs a) {
   // this thread's output element: tile tj, row, col (NT = 2: all 512 threads; NT = 1: the first 256)
   const int tj = NT == 2 ? (tid >> 8) : 0, e = tid & 255;
   const int row = e >> 4, col = e & 15;
-  const int mc = min(m0 + row, M - 1), nc = min(n0 + tj * 16 + col, N - 1);
-  const float bl = *(a.bias ? a.bias + nc : (const float*)a.x);
-  const float pre_bias = a.bias ? bl : 0.f;
-  const float pre_res = ((const float*)a.out)[(long)mc * a.ldo + nc];
+  float pre_bias, pre_res;
+  epi_inputs<true>(a, m0 + row, n0 + tj * 16 + col, pre_bias, pre_res);
   asm volatile("" : "+v"(af[0][0])::"memory");
   f32x4 acc[NT];
 #pragma unroll
@@ -657,43 +711,18 @@ __global__ __launch_bounds__(512) void vcap_rows_gemv8_kernel(RowsGemmArgs a) {
   __syncthreads();
   const bool mine = tid < NT * 256;
   const int ei = tj * 256 + e;
+  const float part = !mine ? 0.f
+                           : ((red[0][ei] + red[1][ei]) + (red[2][ei] + red[3][ei])) +
+                                 ((red[4][ei] + red[5][ei]) + (red[6][ei] + red[7][ei]));
   if constexpr (SPLIT) {
-    // The K-part partials of a column group meet through global memory, the MI355X guide's valid
-    // hand-off form (Guideline 16 R1): every partial store is sc1 (agent-scope relaxed atomic store:
-    // write-through) and every storing wave drains (vmcnt(0)) before the workgroup barrier; then one
-    // lane takes a ticket (agent-scope atomic add, zeroed per decode by vcap_decode_init; KP per group
-    // per launch).  The group's last arriver loads the other parts' partials with sc1 loads and stores
-    // the output; the others exit.  No one waits (no spin), and the sum is
-    // ((p0 + p1) + (p2 + p3)) (KP = 4) or p0 + p1 (KP = 2) whichever arrives last: deterministic.
     const long g = (long)blockIdx.y * (gridDim.x / KP) + grp;
-    float part = 0.f;
-    if (mine) {
-      part = ((red[0][ei] + red[1][ei]) + (red[2][ei] + red[3][ei])) + ((red[4][ei] + red[5][ei]) + (red[6][ei] + red[7][ei]));
-      __hip_atomic_store(a.sk_part + ((g * KP + ksel) * NT) * 256 + ei, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
-    __syncthreads();
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(a.sk_cnt + g, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if ((s_ticket % KP) != KP - 1) return;  // not the last of the group (tickets advance by KP per launch)
-    if (mine && m0 + row < M && n0 + tj * 16 + col < N) {
-      float p[KP];
-#pragma unroll
-      for (int k = 0; k < KP; ++k)
-        p[k] = k == ksel ? part
-                         : __hip_atomic_load(a.sk_part + ((g * KP + k) * NT) * 256 + ei, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-      float v;
-      if constexpr (KP == 4) v = (p[0] + p[1]) + (p[2] + p[3]);
-      else v = p[0] + p[1];
-      ((float*)a.out)[(long)(m0 + row) * a.ldo + n0 + tj * 16 + col] = pre_res + (v + pre_bias);
-    }
+    if (!ksplit_arrive<KP, NT>(a, g, ksel, ei, mine, part)) return;
+    if (mine && m0 + row < M && n0 + tj * 16 + col < N)
+      ((float*)a.out)[(long)(m0 + row) * a.ldo + n0 + tj * 16 + col] =
+          pre_res + (ksplit_sum<KP, NT>(a, g, ksel, ei, part) + pre_bias);
   } else {
-    if (mine && m0 + row < M && n0 + col < N && (hsel < 0 || (col >> 3) == hsel)) {
-      const float v = ((red[0][ei] + red[1][ei]) + (red[2][ei] + red[3][ei])) +
-                      ((red[4][ei] + red[5][ei]) + (red[6][ei] + red[7][ei])) + pre_bias;
-      ((float*)a.out)[(long)(m0 + row) * a.ldo + n0 + col] = pre_res + v;
-    }
+    if (mine && m0 + row < M && n0 + col < N && (hsel < 0 || (col >> 3) == hsel))
+      ((float*)a.out)[(long)(m0 + row) * a.ldo + n0 + col] = pre_res + (part + pre_bias);
   }
 }
 
@@ -751,34 +780,7 @@ __global__ __launch_bounds__(256) void vcap_rows_gemm_lds_kernel(RowsGemmArgs a)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ml = wave + 4 * (gq + r);
-        float s = 0.f;
-#pragma unroll
-        for (int ci = 0; ci < 4; ++ci)
-          if (ci * 256 + lane * 4 < K) s += (xv[r][ci].x + xv[r][ci].y) + (xv[r][ci].z + xv[r][ci].w);
-        const float mean = wave_sum(s) / (float)K;
-        float ss = 0.f;
-#pragma unroll
-        for (int ci = 0; ci < 4; ++ci)
-          if (ci * 256 + lane * 4 < K) {
-            const f32x4 d = xv[r][ci] - mean;
-            ss += sumsq4(d);
-          }
-        const float rstd = rsqrtf(wave_sum(ss) / (float)K + a.ln_eps);
-        const bool live = m0 + ml < M;
-#pragma unroll
-        for (int ci = 0; ci < 4; ++ci) {
-          const int c = ci * 256 + lane * 4;
-          if (c < K) {
-            const f32x4 y = live ? ln_affine4(xv[r][ci], mean, rstd, gv[ci], bv[ci]) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            const int byte = c * (int)sizeof(T);
-            char* dst = dyn + (long)ml * rowb + ((((byte >> 4) ^ (ml & 15))) << 4) + (byte & 15);
-            if constexpr (sizeof(T) == 2) {
-              *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf2(y.x, y.y), pack_bf2(y.z, y.w)};
-            } else {
-              *reinterpret_cast<f32x4*>(dst) = y;
-            }
-          }
-        }
+        ln_row_to_tile<T, 4>(xv[r], gv, bv, K, a.ln_eps, m0 + ml < M, ml, dyn + (long)ml * rowb);
       }
     }
   }
@@ -809,17 +811,9 @@ __global__ __launch_bounds__(256) void vcap_rows_gemm_lds_kernel(RowsGemmArgs a)
   // ---- epilogue inputs
   float pre_bias[NE], pre_res[NE];
 #pragma unroll
-  for (int q = 0; q < NE; ++q) {
-    const int m = m0 + (q / NTB) * 16 + (tid >> 4), n = n0 + (q % NTB) * 16 + (tid & 15);
-    const int mc = min(m, M - 1), nc = min(n, N - 1);
-    // unconditional load (from a valid address when there is no bias), then a select: a load
-    // guarded by the runtime `a.bias` test compiled to a branch + vmcnt(0) that waited for the
-    // whole weight stream before the LayerNorm / A-fragment work could start
-    const float bl = *(a.bias ? a.bias + nc : (const float*)a.x);
-    pre_bias[q] = a.bias ? bl : 0.f;
-    pre_res[q] = 0.f;
-    if constexpr (EPI == EPI_RESID) pre_res[q] = ((const float*)a.out)[(long)mc * a.ldo + nc];
-  }
+  for (int q = 0; q < NE; ++q)
+    epi_inputs<EPI == EPI_RESID>(a, m0 + (q / NTB) * 16 + (tid >> 4), n0 + (q % NTB) * 16 + (tid & 15), pre_bias[q],
+                                 pre_res[q]);
   ProcToks<EPI == EPI_LOGITS ? MT : 1> toks;
   if constexpr (EPI == EPI_LOGITS) toks.load(a, m0);
   if constexpr (PRO == PRO_LN || EPI == EPI_LOGITS) __syncthreads();
@@ -865,7 +859,7 @@ __global__ __launch_bounds__(256) void vcap_rows_gemm_lds_kernel(RowsGemmArgs a)
     for (int j = 0; j < NTB; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave][(i * NTB + j) * 256 + (fg * 4 + r) * 16 + fr] = acc[i][j][r];
-  if constexpr (EPI == EPI_LOGITS) toks.template mark<NTB>(a, m0, n0, s_rep, s_ban);
+  if constexpr (EPI == EPI_LOGITS) toks.mark(a, m0, n0, NTB * 16, &s_rep[0][0], &s_ban[0][0], NTB * 16);
   __syncthreads();
   rows_epilogue<T, MT, NTB, EPI>(a, m0, red, pre_bias, pre_res, lg, s_rep, s_ban, n0);
 }
@@ -936,39 +930,18 @@ __global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __r
     const int page = __shfl(my_page, j >> 4);
     const T* vrow = vc + (((long)page * H + h) * 16 + (j & 15)) * 64 + d8;
     const float p = jj < ctx ? s_p[wave][j] : 0.f;
-    if constexpr (sizeof(T) == 2) {
-      const u32x4 vv = *reinterpret_cast<const u32x4*>(vrow);
-      const unsigned w4[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[2 * e] += p * bf2f((bf16_t)(w4[e] & 0xffff));
-        o[2 * e + 1] += p * bf2f((bf16_t)(w4[e] >> 16));
-      }
-    } else {
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(vrow);
-      const f32x4 v1 = *reinterpret_cast<const f32x4*>(vrow + 4);
+    for (int v = 0; v < 8 / E8; ++v) {
+      float f[E8];
+      chunk_to_f<T>(*reinterpret_cast<const u32x4*>(vrow + v * E8), f);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] += p * v0[e];
-        o[4 + e] += p * v1[e];
-      }
+      for (int e = 0; e < E8; ++e) o[v * E8 + e] += p * f[e];
     }
   }
   // reduce over the 8 key groups: lane ^ 8 (row_ror:8 inside a 16-lane row), then ^16, ^32
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = rows_sum(o[e] + dpp_f<0x128>(o[e]));
-  if (kg == 0) {
-    const float inv = 1.0f / sum;
-    T* orow = out + (long)m * E + h * 64 + d8;
-    if constexpr (sizeof(T) == 2) {
-      *reinterpret_cast<u32x4*>(orow) =
-          (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv),
-                  pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
-    } else {
-      *reinterpret_cast<f32x4*>(orow) = (f32x4){o[0], o[1], o[2], o[3]} * inv;
-      *reinterpret_cast<f32x4*>(orow + 4) = (f32x4){o[4], o[5], o[6], o[7]} * inv;
-    }
-  }
+  if (kg == 0) store_out8<T>(out + (long)m * E + h * 64 + d8, o, 1.0f / sum);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1015,11 +988,9 @@ __global__ __launch_bounds__(256) void vcap_kv_gather_kernel(const T* __restrict
   const T* s = src_pool + l * layer_elems + (long)sr * row_elems;
   T* d = dst_pool + l * layer_elems + (long)r * row_elems;
   const int pages = (len + 15) / 16;
-  const long n = (long)pages * H * 16 * 64 / 8;  // 16-byte chunks for bf16 (8 elems) / 2 for f32
-  const int per = 16 / sizeof(T);
+  const int per = 16 / sizeof(T);  // elements per 16-byte chunk
   for (long i = threadIdx.x; i < (long)pages * H * 16 * 64 / per; i += 256)
     reinterpret_cast<u32x4*>(d)[i] = reinterpret_cast<const u32x4*>(s)[i];
-  (void)n;
 }
 
 // Per-step state init: identity page tables, cleared history / flags.
@@ -1262,11 +1233,33 @@ static int allow_lds(Kern k, int& limit) {
   return limit;
 }
 
+// Which launches split K, and into what: the ONE decision (the dispatcher, the launchers' grids and
+// slab counts and the kernel choice all read its result; a launch without a split reaches the kernels
+// with sk_part / sk_cnt cleared).  Only the mlp c_proj - PRO_DIRECT + EPI_RESID, one 16-column tile
+// per workgroup - at the K of GPT-2 small / medium, and only when the runtime gave both buffers:
+//   bf16, K = 3072: workgroup pairs, vcap_rows_gemv_kernel<bf16, 1, 1, .., 12> in 16-row chunks.
+//     (K = 4096 keeps the one-workgroup tile in bf16: GPT-2-medium's device beam search is priced
+//     against the reference's hypotheses under fp32, test_l14_medium_beam4_bf16_priced_against_reference,
+//     and a beam search's path moves with any change of bf16 summation order.)
+//   f32, K = 3072: 4 K parts x 2-column-tile groups where N is a multiple of 32, else pairs;
+//   f32, K = 4096: pairs - vcap_rows_gemv8_kernel<float, NSL, KP, NT>, 16-row chunks at any M.
+// Anything else (n_embd = 256's K = 1024, wider tiles, other roles) does not split.
+struct KSplit {
+  int kp = 1, nt = 1;  // K parts per column group; 16-column tiles per group
+  bool on() const { return kp > 1; }
+  // workgroups along x: kp per group of nt tiles; unsplit, a.half doubles them
+  int grid_x(int tiles, int half) const { return on() ? tiles / nt * kp : tiles * (half ? 2 : 1); }
+};
+static KSplit rows_split_plan(int dt, int pro, int epi, int ntb, int K, int N, const float* sk_part, const int* sk_cnt) {
+  if (!sk_part || !sk_cnt || pro != PRO_DIRECT || epi != EPI_RESID || ntb != 1) return {};
+  if (dt == VCAP_DT_BF16) return K == 3072 ? KSplit{2, 1} : KSplit{};
+  if (K == 3072) return N % 32 == 0 ? KSplit{4, 2} : KSplit{2, 1};
+  return K == 4096 ? KSplit{2, 1} : KSplit{};
+}
+
 template <typename T, int MT, int NTB, int PRO, int EPI, int NSL>
-static hipError_t launch_gemv(const RowsGemmArgs& a, hipStream_t s) {
-  // the grid doubles for a.half and for the bf16 K split (the kernel's CAN_SPLIT), nothing else
-  const int half = EPI == EPI_RESID && NTB == 1 && (a.half || (sizeof(T) == 2 && a.sk_part)) ? 2 : 1;
-  const dim3 grid(half * ((a.N + NTB * 16 - 1) / (NTB * 16)), (a.M + MT * 16 - 1) / (MT * 16));
+static hipError_t launch_gemv(const RowsGemmArgs& a, KSplit sp, hipStream_t s) {
+  const dim3 grid(sp.grid_x((a.N + NTB * 16 - 1) / (NTB * 16), a.half), (a.M + MT * 16 - 1) / (MT * 16));
   const size_t lds = PRO == PRO_LN ? (size_t)MT * 16 * a.K * sizeof(T) : 0;
   static int limit = 0;
   if ((size_t)allow_lds(vcap_rows_gemv_kernel<T, MT, NTB, PRO, EPI, NSL>, limit) < lds) return hipErrorInvalidValue;
@@ -1285,10 +1278,10 @@ static hipError_t launch_generic(const RowsGemmArgs& a, hipStream_t s) {
 }
 
 template <typename T, int MT, int NTB, int PRO, int EPI, int NSL>
-static bool try_gemv(int nsl, const RowsGemmArgs& a, hipStream_t s, hipError_t& err) {
+static bool try_gemv(int nsl, const RowsGemmArgs& a, KSplit sp, hipStream_t s, hipError_t& err) {
   if constexpr (gemv_fits<T, MT, NTB, PRO, NSL>()) {
     if (nsl == NSL) {
-      err = launch_gemv<T, MT, NTB, PRO, EPI, NSL>(a, s);
+      err = launch_gemv<T, MT, NTB, PRO, EPI, NSL>(a, sp, s);
       return true;
     }
   }
@@ -1296,45 +1289,35 @@ static bool try_gemv(int nsl, const RowsGemmArgs& a, hipStream_t s, hipError_t& 
 }
 
 template <typename T, int MT, int NTB, int PRO, int EPI>
-static hipError_t launch_rows(const RowsGemmArgs& a, hipStream_t s) {
+static hipError_t launch_rows(const RowsGemmArgs& a, KSplit sp, hipStream_t s) {
   // buffer loads address the packed weights (vcap_dec_wload<false>) and a.x (vcap_dec_aload; f32
   // rows under PRO_LN) with 32-bit byte offsets
   if ((long)(a.N + 63) * a.K * (long)sizeof(T) >= 0x7FFFFFFFL ||
       (long)a.M * a.ldx * (long)(PRO == PRO_LN ? sizeof(float) : sizeof(T)) >= 0x7FFFFFFFL)
     return hipErrorInvalidValue;
-  // the bf16 K-split residual GEMV (a.sk_part; the dispatcher sends it in 16-row chunks): each workgroup
-  // streams half the slabs
-  const bool ksplit = sizeof(T) == 2 && a.sk_part && MT == 1 && NTB == 1 && PRO == PRO_DIRECT && EPI == EPI_RESID;
-  const int nsl = a.K / (16 * Frag<T>::kElems) / (ksplit ? 2 : 1);
+  if (sp.on() && !rows_can_split<T, MT, NTB, PRO, EPI>()) return hipErrorInvalidValue;
+  const int nsl = a.K / (16 * Frag<T>::kElems);  // slabs per wave of 4 over the whole K
   hipError_t err = hipSuccess;
-  if (try_gemv<T, MT, NTB, PRO, EPI, 6>(nsl, a, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 8>(nsl, a, s, err) ||
-      try_gemv<T, MT, NTB, PRO, EPI, 12>(nsl, a, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 16>(nsl, a, s, err) ||
-      try_gemv<T, MT, NTB, PRO, EPI, 24>(nsl, a, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 32>(nsl, a, s, err))
-    return err;
+  if (sizeof(T) == 2 || !sp.on()) {  // (the bf16 pair: this GEMV at half the slabs per workgroup)
+    const int n = nsl / sp.kp;
+    if (try_gemv<T, MT, NTB, PRO, EPI, 6>(n, a, sp, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 8>(n, a, sp, s, err) ||
+        try_gemv<T, MT, NTB, PRO, EPI, 12>(n, a, sp, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 16>(n, a, sp, s, err) ||
+        try_gemv<T, MT, NTB, PRO, EPI, 24>(n, a, sp, s, err) || try_gemv<T, MT, NTB, PRO, EPI, 32>(n, a, sp, s, err))
+      return err;
+  }
   if constexpr (sizeof(T) == 4 && NTB == 1 && PRO == PRO_DIRECT && EPI == EPI_RESID) {
-    // f32 mlp c_proj (K = 3072 GPT-2 small / 4096 GPT-2-medium): 8 waves x 24 / 32 slabs, 16-row
-    // chunks over blockIdx.y (r05: the beam searches' 24-32 rows had taken the 64-workgroup
-    // generic kernel, 21 us per launch at K = 4096)
-    const bool split = a.sk_part && a.sk_cnt && (nsl == 48 || nsl == 64);   // any M: 16-row chunks
-    const dim3 grid((split || a.half ? 2 : 1) * ((a.N + 15) / 16), (a.M + 15) / 16);
-    if (split && nsl == 48 && a.N % 32 == 0) {
-      // GPT-2 small: 4 K parts x 2-column-tile groups (the same workgroup count as the pairs)
-      hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 6, 4, 2>), grid, dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
-    if (split) {
-      if (nsl == 48) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 12, 2, 1>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 16, 2, 1>), grid, dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
-    if (nsl == 48 && a.M <= 64) {
-      hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 24, 1, 1>), grid, dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
-    if (nsl == 64 && a.M <= 64) {
-      hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 32, 1, 1>), grid, dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
+    // f32 mlp c_proj (K = 3072 GPT-2 small / 4096 GPT-2-medium): 8 waves, 16-row chunks over
+    // blockIdx.y (r05: the beam searches' 24-32 rows had taken the 64-workgroup generic kernel, 21 us
+    // per launch at K = 4096).  Split: 8 * KP * NSL slabs; unsplit: 24 / 32 slabs per wave, M <= 64
+    const dim3 grid(sp.grid_x((a.N + 15) / 16, a.half), (a.M + 15) / 16), block(512);
+    bool done = true;
+    if (sp.kp == 4) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 6, 4, 2>), grid, block, 0, s, a);
+    else if (sp.kp == 2 && nsl == 48) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 12, 2, 1>), grid, block, 0, s, a);
+    else if (sp.kp == 2) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 16, 2, 1>), grid, block, 0, s, a);
+    else if (nsl == 48 && a.M <= 64) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 24, 1, 1>), grid, block, 0, s, a);
+    else if (nsl == 64 && a.M <= 64) hipLaunchKernelGGL((vcap_rows_gemv8_kernel<float, 32, 1, 1>), grid, block, 0, s, a);
+    else done = false;
+    if (done) return hipGetLastError();
   }
   return launch_generic<T, MT, NTB, PRO, EPI>(a, s);
 }
@@ -1350,22 +1333,26 @@ static hipError_t launch_rows(const RowsGemmArgs& a, hipStream_t s) {
 // Per-element arithmetic (K split over the 4 waves, MFMA order, (w0 + w1) + (w2 + w3) reduction,
 // processors) is that of vcap_rows_gemv_kernel, so logits and ids are bit-identical; the argmax is
 // a total order (value, then lowest index), so its grouping does not matter.
-template <typename T, int NSL, int NTB>
-__global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a, int tpw) {
-  extern __shared__ __attribute__((aligned(16))) char dyn[];  // A tile [16][K] T, then flags
+// The walker shared with vcap_lm_head_lse_kernel (MT row tiles of 16): ln_f tile, weight stream,
+// MFMAs and the (w0 + w1) + (w2 + w3) reduction; what becomes of each logit is the sink's:
+//   sink.issue(a)                  its own loads, issued up front after the first group's weights
+//   sink.ln_copy_row(a, m, K)      where ln_f row m is also kept as f32 (nullptr: nowhere)
+//   sink.tile_ready(a, c0, ncols)  after the barrier that follows the ln_f tile (columns [c0, c0 + ncols))
+//   sink.take(a, i, m, n, v)       logit v of row m (row tile i), column n; each thread meets its
+//                                  (row, col) elements in ascending column order
+//   sink.finish(a, i, m, col)      after the last group: merge the 16 column lanes, write row m's partial
+constexpr int kLmMaxTiles = 32;  // tiles per workgroup of the stream kernel (its flag rows: tpw * 16 bytes)
+template <typename T, int NSL, int NTB, int MT, typename Sink>
+VCAP_DEV void lm_head_walk(const RowsGemmArgs& a, int tpw, char* dyn, float (*red)[MT * NTB * 256], Sink& sink) {
   constexpr int E8 = Frag<T>::kElems, KS = 4 * E8, K = 4 * NSL * KS;
   constexpr int KC = (K + 255) / 256;
-  constexpr int kMaxCols = 32 * 16;  // tpw <= 32
-  __shared__ __attribute__((aligned(16))) float red[4][NTB * 256];
-  unsigned char* s_rep = reinterpret_cast<unsigned char*>(dyn + 16 * K * sizeof(T));
-  unsigned char* s_ban = s_rep + 16 * kMaxCols;
+  constexpr int RPW = MT * 4;  // ln_f rows per wave
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
   const int M = a.M, N = a.N;
   const int nslab = 4 * NSL, g0 = wave * NSL;
   const int ntiles = (N + 15) >> 4;
   const int t0 = blockIdx.x * tpw, t1 = min(t0 + tpw, ntiles);
-  const int c_begin = t0 * 16, ncols = (t1 - t0) * 16;
   const int ngr = (t1 - t0 + NTB - 1) / NTB;
   auto issue = [&](u32x4 (&wf)[NSL][NTB], int gi) {
 #pragma unroll
@@ -1375,11 +1362,11 @@ __global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a
       for (int s = 0; s < NSL; ++s) wf[s][j] = vcap_dec_wload<true>(a.w, wp + s * 64);
     }
   };
-  // first group's weights + ln_f rows + processor token lists, all issued up front
+  // ln_f rows + the first group's weights (+ the sink's loads), all issued up front
   u32x4 wA[NSL][NTB], wB[NSL][NTB];
-  f32x4 xv[4][KC], gv[KC], bv[KC];
+  f32x4 xv[RPW][KC], gv[KC], bv[KC];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
+  for (int r = 0; r < RPW; ++r) {
     const long xo = (long)min(wave + 4 * r, M - 1) * a.ldx;
 #pragma unroll
     for (int c = 0; c < KC; ++c)
@@ -1391,93 +1378,51 @@ __global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a
     bv[c] = *reinterpret_cast<const f32x4*>(a.ln_b + min(c * 256 + lane * 4, K - 4));
   }
   issue(wA, 0);
-  int htk[4], btk[4], nbk[4];
+  sink.issue(a);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = tid + q * 256, m = min(i >> 6, M - 1), t = min(i & 63, a.hist_ld - 1);
-    htk[q] = a.hist[m * a.hist_ld + t];
-    btk[q] = a.banned[m * a.hist_ld + t];
-    nbk[q] = a.nbanned[m];
-  }
-  for (int i = tid; i < 2 * 16 * kMaxCols / 4; i += 256) reinterpret_cast<unsigned*>(s_rep)[i] = 0u;
-  // ln_f (vcap_rows_gemv_kernel PRO_LN arithmetic; the clamped chunks past K do not contribute)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
+  for (int r = 0; r < RPW; ++r) {
     const int m = wave + 4 * r;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-      if (c * 256 + lane * 4 < K) s += (xv[r][c].x + xv[r][c].y) + (xv[r][c].z + xv[r][c].w);
-    const float mean = wave_sum(s) / (float)K;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-      if (c * 256 + lane * 4 < K) {
-        const f32x4 d = xv[r][c] - mean;
-        ss += sumsq4(d);
-      }
-    const float rstd = rsqrtf(wave_sum(ss) / (float)K + a.ln_eps);
-    const bool live = m < M;
-#pragma unroll
-    for (int c = 0; c < KC; ++c) {
-      if (c * 256 + lane * 4 < K) {
-        const f32x4 y = live ? ln_affine4(xv[r][c], mean, rstd, gv[c], bv[c]) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (a.screen_h && blockIdx.x == 0 && live)
-          *reinterpret_cast<f32x4*>(a.screen_h + (long)m * K + c * 256 + lane * 4) = y;
-        const int byte = (c * 256 + lane * 4) * (int)sizeof(T);
-        char* dst = dyn + (long)m * (K * (int)sizeof(T)) + ((((byte >> 4) ^ (m & 15))) << 4) + (byte & 15);
-        if constexpr (sizeof(T) == 2) {
-          *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf2(y.x, y.y), pack_bf2(y.z, y.w)};
-        } else {
-          *reinterpret_cast<f32x4*>(dst) = y;
-        }
-      }
-    }
+    ln_row_to_tile<T, KC>(xv[r], gv, bv, K, a.ln_eps, m < M, m, dyn + (long)m * (K * (int)sizeof(T)),
+                          sink.ln_copy_row(a, m, K));
   }
-  __syncthreads();  // flags zeroed, A tile written
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = tid + q * 256, m = i >> 6, t = i & 63;
-    if (m >= M) continue;
-    const unsigned hc = (unsigned)(htk[q] - c_begin), bc = (unsigned)(btk[q] - c_begin);
-    if (a.rep_penalty != 1.0f && t < a.gen_len && hc < (unsigned)ncols) s_rep[m * kMaxCols + hc] = 1;
-    if (t < nbk[q] && bc < (unsigned)ncols) s_ban[m * kMaxCols + bc] = 1;
-  }
-  __syncthreads();
+  __syncthreads();  // A tile written
+  sink.tile_ready(a, t0 * 16, (t1 - t0) * 16);
   const int row = tid >> 4, col = tid & 15;
-  float bv_run = -INFINITY;
-  int bi_run = 0x7fffffff;
   auto group = [&](const u32x4 (&wf)[NSL][NTB], int gi) {
-    f32x4 acc[NTB];
+    f32x4 acc[MT][NTB];
 #pragma unroll
-    for (int j = 0; j < NTB; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int j = 0; j < NTB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < NSL; ++s) {
       const int chunk = (g0 + s) * 4 + fg;
-      const u32x4 A = *reinterpret_cast<const u32x4*>(dyn + (long)fr * K * sizeof(T) + ((chunk ^ fr) << 4));
 #pragma unroll
-      for (int j = 0; j < NTB; ++j) acc[j] = mfma_frag(A, wf[s][j], acc[j], (T*)nullptr);
+      for (int i = 0; i < MT; ++i) {
+        const int ar = i * 16 + fr;
+        const u32x4 A = *reinterpret_cast<const u32x4*>(dyn + (long)ar * K * sizeof(T) + ((chunk ^ fr) << 4));
+#pragma unroll
+        for (int j = 0; j < NTB; ++j) acc[i][j] = mfma_frag(A, wf[s][j], acc[i][j], (T*)nullptr);
+      }
     }
 #pragma unroll
-    for (int j = 0; j < NTB; ++j)
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][j * 256 + (fg * 4 + r) * 16 + fr] = acc[j][r];
+      for (int j = 0; j < NTB; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[wave][(i * NTB + j) * 256 + (fg * 4 + r) * 16 + fr] = acc[i][j][r];
     __syncthreads();
-    if (row < M) {
 #pragma unroll
-      for (int j = 0; j < NTB; ++j) {
-        const int t = t0 + gi * NTB + j, n = t * 16 + col;
-        if (t < t1 && n < N) {
-          const int e = j * 256 + row * 16 + col;
-          const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]) + 0.f;
-          if (a.logits_raw) a.logits_raw[(long)row * N + n] = v;
-          float sv = v;
-          const int li = row * kMaxCols + (n - c_begin);
-          if (s_rep[li]) sv = sv < 0.f ? sv * a.rep_penalty : sv / a.rep_penalty;
-          if (s_ban[li]) sv = -INFINITY;
-          if (n == a.eos && a.gen_len < a.min_new) sv = -INFINITY;
-          if (a.proc_out) a.proc_out[(long)row * N + n] = sv;
-          argmax_take(bv_run, bi_run, sv, n);
+    for (int i = 0; i < MT; ++i) {
+      const int m = i * 16 + row;
+      if (m < M) {
+#pragma unroll
+        for (int j = 0; j < NTB; ++j) {
+          const int t = t0 + gi * NTB + j, n = t * 16 + col;
+          if (t < t1 && n < N) {
+            const int e = (i * NTB + j) * 256 + row * 16 + col;
+            sink.take(a, i, m, n, (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]) + 0.f);
+          }
         }
       }
     }
@@ -1491,34 +1436,87 @@ __global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a
       group(wB, gi + 1);
     }
   }
-  argmax_take(bv_run, bi_run, dpp_f<DPP_XOR1>(bv_run), dpp_i<DPP_XOR1>(bi_run));
-  argmax_take(bv_run, bi_run, dpp_f<DPP_XOR2>(bv_run), dpp_i<DPP_XOR2>(bi_run));
-  argmax_take(bv_run, bi_run, dpp_f<DPP_HALF_MIRROR>(bv_run), dpp_i<DPP_HALF_MIRROR>(bi_run));
-  argmax_take(bv_run, bi_run, dpp_f<DPP_MIRROR>(bv_run), dpp_i<DPP_MIRROR>(bi_run));
-  if (col == 0 && row < M) {
-    a.part_val[(long)row * gridDim.x + blockIdx.x] = bv_run;
-    a.part_idx[(long)row * gridDim.x + blockIdx.x] = bi_run;
-  }
+#pragma unroll
+  for (int i = 0; i < MT; ++i) sink.finish(a, i, i * 16 + row, col);
 }
 
-template <typename T, int NSL>
-static bool launch_lm_stream(const RowsGemmArgs& a, int* nblk_out, hipStream_t s, hipError_t& err,
-                             int* tpb_out = nullptr) {
-  constexpr int NTB = (NSL <= 8) ? 4 : 2;  // two register sets of NSL x NTB fragments
+// Greedy sink: processors per element, a running argmax per row, one (max, index) partial per row.
+struct LmArgmaxSink {
+  unsigned char *s_rep, *s_ban;  // [16][kLmMaxTiles * 16] token flags of the workgroup's columns
+  int c_begin;
+  ProcToks<1> toks;
+  float bv;  // running argmax of this thread's (row, col) elements
+  int bi;
+  VCAP_DEV void issue(const RowsGemmArgs& a) {
+    toks.load(a, 0);
+    for (int i = threadIdx.x; i < 2 * 16 * kLmMaxTiles * 16 / 4; i += 256) reinterpret_cast<unsigned*>(s_rep)[i] = 0u;
+  }
+  VCAP_DEV float* ln_copy_row(const RowsGemmArgs& a, int m, int K) const {  // the screen's: workgroup 0 only
+    return a.screen_h && blockIdx.x == 0 ? a.screen_h + (long)m * K : nullptr;
+  }
+  VCAP_DEV void tile_ready(const RowsGemmArgs& a, int c0, int ncols) {  // (the barrier: flags zeroed too)
+    c_begin = c0;
+    toks.mark(a, 0, c0, ncols, s_rep, s_ban, kLmMaxTiles * 16);
+    __syncthreads();
+    bv = -INFINITY;
+    bi = 0x7fffffff;
+  }
+  VCAP_DEV void take(const RowsGemmArgs& a, int, int m, int n, float v) {
+    if (a.logits_raw) a.logits_raw[(long)m * a.N + n] = v;
+    const int li = m * (kLmMaxTiles * 16) + (n - c_begin);
+    const float sv = apply_processors(a, v, s_rep[li], s_ban[li], n);
+    if (a.proc_out) a.proc_out[(long)m * a.N + n] = sv;
+    argmax_take(bv, bi, sv, n);
+  }
+  VCAP_DEV void finish(const RowsGemmArgs& a, int, int m, int col) {
+    argmax_take(bv, bi, dpp_f<DPP_XOR1>(bv), dpp_i<DPP_XOR1>(bi));
+    argmax_take(bv, bi, dpp_f<DPP_XOR2>(bv), dpp_i<DPP_XOR2>(bi));
+    argmax_take(bv, bi, dpp_f<DPP_HALF_MIRROR>(bv), dpp_i<DPP_HALF_MIRROR>(bi));
+    argmax_take(bv, bi, dpp_f<DPP_MIRROR>(bv), dpp_i<DPP_MIRROR>(bi));
+    if (col == 0 && m < a.M) {
+      a.part_val[(long)m * gridDim.x + blockIdx.x] = bv;
+      a.part_idx[(long)m * gridDim.x + blockIdx.x] = bi;
+    }
+  }
+};
+
+template <typename T, int NSL, int NTB>
+__global__ __launch_bounds__(256) void vcap_lm_head_stream_kernel(RowsGemmArgs a, int tpw) {
+  extern __shared__ __attribute__((aligned(16))) char dyn[];  // A tile [16][K] T, then flags
+  __shared__ __attribute__((aligned(16))) float red[4][NTB * 256];
+  LmArgmaxSink sink;
+  sink.s_rep = reinterpret_cast<unsigned char*>(dyn + 16 * (4 * NSL * 4 * Frag<T>::kElems) * sizeof(T));
+  sink.s_ban = sink.s_rep + 16 * kLmMaxTiles * 16;
+  lm_head_walk<T, NSL, NTB, 1>(a, tpw, dyn, red, sink);
+}
+
+// Launch of either lm_head weight-stream kernel over `cus` workgroups at most; false (nothing
+// launched) where the kernel does not apply: more than max_tpw tiles per workgroup, more partials
+// than max_grid, or an LDS limit that cannot be raised - the 64-column GEMV blocks take the lm_head.
+template <typename Kern>
+static bool launch_lm_walk(Kern kern, int& limit, const RowsGemmArgs& a, int cus, size_t lds, int max_tpw, int max_grid,
+                           int* nblk_out, int* tpb_out, hipStream_t s, hipError_t& err) {
   const int ntiles = (a.N + 15) / 16;
-  const int cus = vcap_device_cus();
   const int tpw = (ntiles + cus - 1) / cus;
-  const size_t lds = (size_t)16 * (4 * NSL * 4 * Frag<T>::kElems) * sizeof(T) + 2 * 16 * 32 * 16;
-  static int limit = 0;
-  // a vocabulary that needs > 32 tiles per CU (a device or partition with few CUs), or a kernel whose
-  // LDS limit cannot be raised: not this kernel - the 64-column GEMV blocks take the lm_head
-  if (tpw > 32 || (size_t)allow_lds(vcap_lm_head_stream_kernel<T, NSL, NTB>, limit) < lds) return false;
   const int grid = (ntiles + tpw - 1) / tpw;
-  hipLaunchKernelGGL((vcap_lm_head_stream_kernel<T, NSL, NTB>), dim3(grid), dim3(256), lds, s, a, tpw);
+  if (tpw > max_tpw || grid > max_grid || (size_t)allow_lds(kern, limit) < lds) return false;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, tpw);
   if (nblk_out) *nblk_out = grid;
   if (tpb_out) *tpb_out = tpw;
   err = hipGetLastError();
   return true;
+}
+
+// one workgroup per CU; a vocabulary that needs > kLmMaxTiles tiles per CU (a device or partition
+// with few CUs) is not this kernel's
+template <typename T, int NSL>
+static bool launch_lm_stream(const RowsGemmArgs& a, int* nblk_out, hipStream_t s, hipError_t& err,
+                             int* tpb_out = nullptr) {
+  constexpr int NTB = (NSL <= 8) ? 4 : 2;  // two register sets of NSL x NTB fragments
+  const size_t lds = (size_t)16 * (4 * NSL * 4 * Frag<T>::kElems) * sizeof(T) + 2 * 16 * kLmMaxTiles * 16;
+  static int limit = 0;
+  return launch_lm_walk(vcap_lm_head_stream_kernel<T, NSL, NTB>, limit, a, vcap_device_cus(), lds, kLmMaxTiles,
+                        0x7fffffff, nblk_out, tpb_out, s, err);
 }
 
 // M <= 16 lm_head as the weight stream above; returns false where it does not apply
@@ -1558,173 +1556,61 @@ hipError_t vcap_lm_head_screen_dispatch(const RowsGemmArgs& a, int* nblk_out, in
 // workgroup leaves one (max, sum exp(x - max)) partial per row, kept online per thread and merged
 // over the 16 column lanes - the quantity of the GEMV epilogue's two-pass form (its rounding differs
 // at the ulp level), merged by vcap_beam_cand_kernel the same way over nblk = grid partials.
-template <typename T, int NSL, int NTB, int MT>
-__global__ __launch_bounds__(256) void vcap_lm_head_lse_kernel(RowsGemmArgs a, int tpw) {
-  extern __shared__ __attribute__((aligned(16))) char dyn[];  // A tile [MT * 16][K] T
-  constexpr int E8 = Frag<T>::kElems, KS = 4 * E8, K = 4 * NSL * KS;
-  constexpr int KC = (K + 255) / 256;
-  constexpr int RPW = MT * 4;  // ln_f rows per wave
-  __shared__ __attribute__((aligned(16))) float red[4][MT * NTB * 256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fg = lane >> 4;
-  const int M = a.M, N = a.N;
-  const int nslab = 4 * NSL, g0 = wave * NSL;
-  const int ntiles = (N + 15) >> 4;
-  const int t0 = blockIdx.x * tpw, t1 = min(t0 + tpw, ntiles);
-  const int ngr = (t1 - t0 + NTB - 1) / NTB;
-  auto issue = [&](u32x4 (&wf)[NSL][NTB], int gi) {
-#pragma unroll
-    for (int j = 0; j < NTB; ++j) {
-      const u32x4* wp = packed_frag(a.w, min(t0 + gi * NTB + j, t1 - 1), nslab, g0, lane);
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) wf[s][j] = vcap_dec_wload<true>(a.w, wp + s * 64);
-    }
-  };
-  // ln_f rows + the first group's weights, issued up front
-  u32x4 wA[NSL][NTB], wB[NSL][NTB];
-  f32x4 xv[RPW][KC], gv[KC], bv[KC];
-#pragma unroll
-  for (int r = 0; r < RPW; ++r) {
-    const long xo = (long)min(wave + 4 * r, M - 1) * a.ldx;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-      xv[r][c] = __builtin_bit_cast(f32x4, vcap_dec_aload(a.x, (xo + min(c * 256 + lane * 4, K - 4)) * 4L));
-  }
-#pragma unroll
-  for (int c = 0; c < KC; ++c) {
-    gv[c] = *reinterpret_cast<const f32x4*>(a.ln_g + min(c * 256 + lane * 4, K - 4));
-    bv[c] = *reinterpret_cast<const f32x4*>(a.ln_b + min(c * 256 + lane * 4, K - 4));
-  }
-  issue(wA, 0);
-  // ln_f (vcap_rows_gemv_kernel PRO_LN arithmetic; the clamped chunks past K do not contribute)
-#pragma unroll
-  for (int r = 0; r < RPW; ++r) {
-    const int m = wave + 4 * r;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-      if (c * 256 + lane * 4 < K) s += (xv[r][c].x + xv[r][c].y) + (xv[r][c].z + xv[r][c].w);
-    const float mean = wave_sum(s) / (float)K;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-      if (c * 256 + lane * 4 < K) {
-        const f32x4 d = xv[r][c] - mean;
-        ss += sumsq4(d);
-      }
-    const float rstd = rsqrtf(wave_sum(ss) / (float)K + a.ln_eps);
-    const bool live = m < M;
-#pragma unroll
-    for (int c = 0; c < KC; ++c) {
-      if (c * 256 + lane * 4 < K) {
-        const f32x4 y = live ? ln_affine4(xv[r][c], mean, rstd, gv[c], bv[c]) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        const int byte = (c * 256 + lane * 4) * (int)sizeof(T);
-        char* dst = dyn + (long)m * (K * (int)sizeof(T)) + ((((byte >> 4) ^ (m & 15))) << 4) + (byte & 15);
-        if constexpr (sizeof(T) == 2) {
-          *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf2(y.x, y.y), pack_bf2(y.z, y.w)};
-        } else {
-          *reinterpret_cast<f32x4*>(dst) = y;
-        }
-      }
-    }
-  }
-  __syncthreads();  // A tile written
-  const int row = tid >> 4, col = tid & 15;
+// LSE sink: the raw logit stored, an online (max, sum exp(x - max)) per thread and row tile.
+template <int MT>
+struct LmLseSink {
   float rmx[MT], rsm[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    rmx[i] = -INFINITY;
-    rsm[i] = 0.f;
-  }
-  auto group = [&](const u32x4 (&wf)[NSL][NTB], int gi) {
-    f32x4 acc[MT][NTB];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NTB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const int chunk = (g0 + s) * 4 + fg;
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        const int ar = i * 16 + fr;
-        const u32x4 A = *reinterpret_cast<const u32x4*>(dyn + (long)ar * K * sizeof(T) + ((chunk ^ fr) << 4));
-#pragma unroll
-        for (int j = 0; j < NTB; ++j) acc[i][j] = mfma_frag(A, wf[s][j], acc[i][j], (T*)nullptr);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NTB; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[wave][(i * NTB + j) * 256 + (fg * 4 + r) * 16 + fr] = acc[i][j][r];
-    __syncthreads();
+  VCAP_DEV void issue(const RowsGemmArgs&) {}
+  VCAP_DEV float* ln_copy_row(const RowsGemmArgs&, int, int) const { return nullptr; }
+  VCAP_DEV void tile_ready(const RowsGemmArgs&, int, int) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-      const int m = i * 16 + row;
-      if (m < M) {
-#pragma unroll
-        for (int j = 0; j < NTB; ++j) {
-          const int t = t0 + gi * NTB + j, n = t * 16 + col;
-          if (t < t1 && n < N) {
-            const int e = (i * NTB + j) * 256 + row * 16 + col;
-            const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]) + 0.f;
-            a.logits_raw[(long)m * N + n] = v;
-            const float nm = fmaxf(rmx[i], v);
-            rsm[i] = rsm[i] * expf(rmx[i] - nm) + expf(v - nm);
-            rmx[i] = nm;
-          }
-        }
-      }
-    }
-    __syncthreads();
-  };
-  for (int gi = 0; gi < ngr; gi += 2) {
-    if (gi + 1 < ngr) issue(wB, gi + 1);
-    group(wA, gi);
-    if (gi + 1 < ngr) {
-      if (gi + 2 < ngr) issue(wA, gi + 2);
-      group(wB, gi + 1);
+      rmx[i] = -INFINITY;
+      rsm[i] = 0.f;
     }
   }
-  // merge the 16 column lanes' partials of each row (a lane that saw no column holds (-inf, 0))
-  auto merge = [](float& m, float& s, float om, float os) {
-    const float nm = fmaxf(m, om);
-    s = s * (m == nm ? 1.f : expf(m - nm)) + os * (om == nm ? 1.f : expf(om - nm));
-    m = nm;
-  };
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
+  VCAP_DEV void take(const RowsGemmArgs& a, int i, int m, int n, float v) {
+    a.logits_raw[(long)m * a.N + n] = v;
+    const float nm = fmaxf(rmx[i], v);
+    rsm[i] = rsm[i] * expf(rmx[i] - nm) + expf(v - nm);
+    rmx[i] = nm;
+  }
+  // merge the 16 column lanes' partials of the row (a lane that saw no column holds (-inf, 0))
+  VCAP_DEV void finish(const RowsGemmArgs& a, int i, int m, int col) {
+    auto merge = [](float& mx, float& sm, float omx, float osm) {
+      const float nm = fmaxf(mx, omx);
+      sm = sm * (mx == nm ? 1.f : expf(mx - nm)) + osm * (omx == nm ? 1.f : expf(omx - nm));
+      mx = nm;
+    };
     merge(rmx[i], rsm[i], dpp_f<DPP_XOR1>(rmx[i]), dpp_f<DPP_XOR1>(rsm[i]));
     merge(rmx[i], rsm[i], dpp_f<DPP_XOR2>(rmx[i]), dpp_f<DPP_XOR2>(rsm[i]));
     merge(rmx[i], rsm[i], dpp_f<DPP_HALF_MIRROR>(rmx[i]), dpp_f<DPP_HALF_MIRROR>(rsm[i]));
     merge(rmx[i], rsm[i], dpp_f<DPP_MIRROR>(rmx[i]), dpp_f<DPP_MIRROR>(rsm[i]));
-    const int m = i * 16 + row;
-    if (col == 0 && m < M) {
+    if (col == 0 && m < a.M) {
       a.part_val[(long)m * gridDim.x + blockIdx.x] = rmx[i];
       a.part_sum[(long)m * gridDim.x + blockIdx.x] = rsm[i];
     }
   }
+};
+
+template <typename T, int NSL, int NTB, int MT>
+__global__ __launch_bounds__(256) void vcap_lm_head_lse_kernel(RowsGemmArgs a, int tpw) {
+  extern __shared__ __attribute__((aligned(16))) char dyn[];  // A tile [MT * 16][K] T
+  __shared__ __attribute__((aligned(16))) float red[4][MT * NTB * 256];
+  LmLseSink<MT> sink;
+  lm_head_walk<T, NSL, NTB, MT>(a, tpw, dyn, red, sink);
 }
 
+// one workgroup per CU, or per a.max_blocks (a beam search sharing the GPU with an encode); never
+// more partials than the caller's buffers hold (a.nblk)
 template <typename T, int NSL, int MT>
 static bool launch_lm_lse(const RowsGemmArgs& a, int* nblk_out, hipStream_t s, hipError_t& err) {
   constexpr int NTB = (NSL <= 8) ? 4 : 2;  // two register sets of MT x NSL x NTB fragments
-  const int ntiles = (a.N + 15) / 16;
-  // one workgroup per CU, or per a.max_blocks (a beam search sharing the GPU with an encode)
   const int cus = a.max_blocks > 0 ? std::min(vcap_device_cus(), a.max_blocks) : vcap_device_cus();
-  const int tpw = (ntiles + cus - 1) / cus;
-  const int grid = (ntiles + tpw - 1) / tpw;
   const size_t lds = (size_t)MT * 16 * (4 * NSL * 4 * Frag<T>::kElems) * sizeof(T);
   static int limit = 0;
-  // more partials than the caller's buffers hold, or an LDS limit that cannot be raised: the
-  // 64-column GEMV blocks take the lm_head
-  if (grid > a.nblk || (size_t)allow_lds(vcap_lm_head_lse_kernel<T, NSL, NTB, MT>, limit) < lds) return false;
-  hipLaunchKernelGGL((vcap_lm_head_lse_kernel<T, NSL, NTB, MT>), dim3(grid), dim3(256), lds, s, a, tpw);
-  if (nblk_out) *nblk_out = grid;
-  err = hipGetLastError();
-  return true;
+  return launch_lm_walk(vcap_lm_head_lse_kernel<T, NSL, NTB, MT>, limit, a, cus, lds, 0x7fffffff, a.nblk, nblk_out,
+                        nullptr, s, err);
 }
 
 static bool try_lm_lse(int dt, const RowsGemmArgs& a, int* nblk_out, hipStream_t s, hipError_t& err) {
@@ -1783,29 +1669,18 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
   const int tiles = (a.N + 15) / 16;
   ah.half = pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && a.M <= 32 &&
             (a.max_blocks <= 0 ? 2 * tiles <= vcap_device_cus() : 2 * tiles <= a.max_blocks);
-  // f32 LayerNorm-prologue rows of > 512 features in 32-row chunks would need > 64 KiB of A tile
-  // beside the split-K buffers (GPT-2-medium fp32 beam search: 32 x 1024 x 4 B + 32 KiB > 160 KiB):
-  // such launches take 16-row chunks (two blockIdx.y chunks per 32 rows)
-  // the bf16 mlp c_proj K split (GPT-2 small's K = 3072, whole tiles) runs in 16-row chunks at every row
-  // count; elsewhere a bf16 launch ignores sk_part.  (GPT-2-medium's K = 4096 keeps the one-workgroup
-  // tile in bf16: its device beam search is priced against the reference's hypotheses under fp32
-  // (test_l14_medium_beam4_bf16_priced_against_reference), and a beam search's path moves with any
-  // change of bf16 summation order.)
-  // the f32 K split is vcap_rows_gemv8_kernel's alone: PRO_DIRECT + EPI_RESID, one tile per workgroup
-  // and K / 64 = 48 or 64 slabs (K = 3072 / 4096); every other f32 launch drops sk_part here, so
-  // the flag the runtime sets on each mlp c_proj never reaches a kernel or a grid that does not
-  // implement the split (n_embd = 256: K = 1024 is vcap_rows_gemv_kernel<float, .., 16>, whose
-  // CAN_SPLIT and launch_gemv's grid doubling are bf16-only for the same reason)
-  const bool bf16_split_ok = pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && a.K == 3072;
-  const bool f32_split_ok = pro == PRO_DIRECT && epi == EPI_RESID && ntb == 1 && (a.K / 64 == 48 || a.K / 64 == 64);
-  if (ah.sk_part && !(dt == VCAP_DT_BF16 ? bf16_split_ok : f32_split_ok)) {
+  // a launch that does not split carries no sk pointers: the kernels' run-time split flag is a.sk_part
+  const KSplit sp = rows_split_plan(dt, pro, epi, ntb, a.K, a.N, a.sk_part, a.sk_cnt);
+  if (!sp.on()) {
     ah.sk_part = nullptr;
     ah.sk_cnt = nullptr;
   }
-  const bool bsplit = dt == VCAP_DT_BF16 && ah.sk_part;
-  const bool one = a.M <= 16 || bsplit || (pro == PRO_LN && dt != VCAP_DT_BF16 && a.K > 512);
+  // 16-row chunks (MT = 1) for M <= 16, for the bf16 K split, and for f32 LayerNorm-prologue rows of
+  // > 512 features, which in 32-row chunks would need > 64 KiB of A tile beside the split-K buffers
+  // (GPT-2-medium fp32 beam search: 32 x 1024 x 4 B + 32 KiB > 160 KiB)
+  const bool one = a.M <= 16 || (dt == VCAP_DT_BF16 && sp.on()) || (pro == PRO_LN && dt != VCAP_DT_BF16 && a.K > 512);
 #define VCAP_ROWS(TT, PP, EE, NT) \
-  return one ? launch_rows<TT, 1, NT, PP, EE>(ah, s) : launch_rows<TT, 2, NT, PP, EE>(ah, s);
+  return one ? launch_rows<TT, 1, NT, PP, EE>(ah, sp, s) : launch_rows<TT, 2, NT, PP, EE>(ah, sp, s);
 #define VCAP_ROWS_NT(TT, PP, EE)            \
   if (ntb == 4) { VCAP_ROWS(TT, PP, EE, 4) } \
   if (ntb == 2) { VCAP_ROWS(TT, PP, EE, 2) } \
@@ -1848,59 +1723,41 @@ size_t vcap_rows_packed_size(int dt, int N, int K) {
   return (size_t)((N + 15) / 16) * (size_t)(K / ks) * 1024;
 }
 
-// bf16 fast path for contexts of at most 64 positions with the contiguous page layout the
+// Fast path for contexts of at most 64 positions with the contiguous page layout the
 // runtime allocates (page of position j of sequence `seq` = seq * maxp + j / 16, i.e. the identity
 // page table): page ids are computed, not loaded, and q, the lane's K row and all of its V rows
 // are issued together, so the wave pays ONE memory round trip instead of three
 // (page table -> K -> V).  Arithmetic identical to vcap_decode_attention_kernel.
-__global__ __launch_bounds__(64) void vcap_decode_attention_c64_kernel(const bf16_t* __restrict__ q,
-                                                                       const bf16_t* __restrict__ kc,
-                                                                       const bf16_t* __restrict__ vc, int maxp,
-                                                                       bf16_t* __restrict__ out, int M, int H,
-                                                                       int S_new, int past) {
-  __shared__ float s_q[64];
+template <typename T>
+__global__ __launch_bounds__(64) void vcap_decode_attention_c64_kernel(const T* __restrict__ q, const T* __restrict__ kc,
+                                                                       const T* __restrict__ vc, int maxp,
+                                                                       T* __restrict__ out, int M, int H, int S_new,
+                                                                       int past) {
+  __shared__ __attribute__((aligned(16))) float s_q[64];
   __shared__ float s_p[64];
   const int item = blockIdx.x;  // one 64-thread workgroup per (row, head)
   if (item >= M * H) return;
   const int m = item / H, h = item - m * H;
   const int seq = m / S_new, qpos = past + (m - seq * S_new);
   const int ctx = qpos + 1;  // <= 64 (dispatcher)
-  C64Loads L;
-  c64_issue(L, q, kc, vc, maxp, m, h, H, seq, ctx);
-  c64_finish(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64);
-}
-
-__global__ __launch_bounds__(64) void vcap_decode_attention_c64f_kernel(const float* __restrict__ q,
-                                                                        const float* __restrict__ kc,
-                                                                        const float* __restrict__ vc, int maxp,
-                                                                        float* __restrict__ out, int M, int H,
-                                                                        int S_new, int past) {
-  __shared__ __attribute__((aligned(16))) float s_q[64];
-  __shared__ float s_p[64];
-  const int item = blockIdx.x;
-  if (item >= M * H) return;
-  const int m = item / H, h = item - m * H;
-  const int seq = m / S_new, qpos = past + (m - seq * S_new);
-  const int ctx = qpos + 1;  // <= 64 (dispatcher)
-  C64LoadsF L;
-  c64f_issue(L, q, kc, vc, maxp, m, h, H, seq, ctx);
-  c64f_finish(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64);
+  C64Loads<T> L;
+  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);
+  c64_finish<T>(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64);
 }
 
 hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
                                           int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s) {
   if (past + S_new > 1024 || maxp > 64) return hipErrorInvalidValue;
   const dim3 grid((M * H + 3) / 4), block(256);
-  if (dt == VCAP_DT_BF16 && !pt && past + S_new <= 64) {
+  if (!pt && past + S_new <= 64 && (dt == VCAP_DT_BF16 || dt == VCAP_DT_F32)) {
     // one 64-thread workgroup per (row, head): the ~100-200 items of a decode step spread over as
     // many CUs (each item's q / K / V round trip on a CU of its own) instead of 4 per CU
-    hipLaunchKernelGGL(vcap_decode_attention_c64_kernel, dim3(M * H), dim3(64), 0, s, (const bf16_t*)q,
-                       (const bf16_t*)kc, (const bf16_t*)vc, maxp, (bf16_t*)out, M, H, S_new, past);
-    return hipGetLastError();
-  }
-  if (dt == VCAP_DT_F32 && !pt && past + S_new <= 64) {
-    hipLaunchKernelGGL(vcap_decode_attention_c64f_kernel, dim3(M * H), dim3(64), 0, s, (const float*)q,
-                       (const float*)kc, (const float*)vc, maxp, (float*)out, M, H, S_new, past);
+    if (dt == VCAP_DT_BF16)
+      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<bf16_t>), dim3(M * H), dim3(64), 0, s, (const bf16_t*)q,
+                         (const bf16_t*)kc, (const bf16_t*)vc, maxp, (bf16_t*)out, M, H, S_new, past);
+    else
+      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<float>), dim3(M * H), dim3(64), 0, s, (const float*)q,
+                         (const float*)kc, (const float*)vc, maxp, (float*)out, M, H, S_new, past);
     return hipGetLastError();
   }
   if (!pt) return hipErrorInvalidValue;  // the general kernels read the page table
