@@ -269,14 +269,28 @@ def generate_raw_greedy(sd, arch, inputs_embeds: Tensor, *, max_new_tokens: int 
 
 def generate_beam(sd, arch, inputs_embeds: Tensor, *, num_beams: int, max_new_tokens: int, min_new_tokens: int = 8,
                   repetition_penalty: float = 1.1, no_repeat_ngram_size: int = 3, length_penalty: float = 1.0,
-                  eos_token_id: Optional[int] = None) -> List[List[int]]:
+                  eos_token_id: Optional[int] = None, trace: Optional[dict] = None) -> List[List[int]]:
     """HF GenerationMixin._beam_search (transformers 5.15.0 generation/utils.py, as
     text_decoder.py:131-144 reaches it with inputs_embeds: prompt length 0, early_stopping False)
     restated on the CPU: log_softmax -> processors -> + running beam scores -> top-2k over
     beams x vocab -> running / finished updates -> cache reorder; stop when no batch can improve
     or every candidate hit EOS / max length.  Returns each sequence's best finished hypothesis
     (the first max(length) tokens, EOS-padded) - pinned to the reference's beam3 / beam4 goldens
-    (tests/test_cpu_oracle.py)."""
+    and to transformers' own EOS-rich searches (tests/golden/beam_eos, tests/test_cpu_oracle.py).
+
+    `trace`, when given, is a dict this fills (the ids returned do not change):
+      lengths [B]            generated length of each best hypothesis
+      steps                  number of select steps executed; stopped_early = steps < max_new_tokens
+      sat_step [B]           step at which the sequence stopped being able to improve (None: never)
+      events [B]             counters over the steps the sequence was still improvable: `did` (EOS in
+                             the first nb of the top-2nb), `late` (EOS in ranks nb..2nb-1), `evict`
+                             (a finished hypothesis pushed out of the best nb by a better one),
+                             `best_replaced` (a newer hypothesis took the best place from an older)
+      margins [B][step]      the smallest gap behind any decision of that step, taken while the
+                             sequence is improvable, entries at or below -1e8 ignored: consecutive
+                             gaps of the top 2nb+1 of lp + running score (the last is the membership
+                             gap), consecutive gaps of the top nb+1 merged finished scores, and
+                             |best running - worst finished| where a finished hypothesis exists."""
     eos = arch.eos_token_id if eos_token_id is None else eos_token_id
     B, nb = inputs_embeds.shape[0], num_beams
     V, L, K = arch.vocab, max_new_tokens, 2 * num_beams
@@ -293,6 +307,12 @@ def generate_beam(sd, arch, inputs_embeds: Tensor, *, num_beams: int, max_new_to
     fin = torch.zeros(B, nb, dtype=torch.bool)
     unsat = torch.ones(B, dtype=torch.bool)
     take = lambda t, i: torch.stack([t[b][i[b]] for b in range(B)])  # noqa: E731
+    if trace is not None:
+        trace.update(sat_step=[None] * B, margins=[[] for _ in range(B)], steps=0,
+                     events=[dict(did=0, late=0, evict=0, best_replaced=0) for _ in range(B)])
+
+    def gaps(v):   # consecutive gaps of a descending list, pairs touching a masked entry dropped
+        return [float(a - b) for a, b in zip(v[:-1], v[1:]) if b > -1.0e8]
     for cur in range(L):
         lp = torch.log_softmax(logits, dim=-1)
         lp = process_logits(lp, run_seq[:, :, :cur].reshape(B * nb, cur), repetition_penalty=repetition_penalty,
@@ -312,16 +332,38 @@ def generate_beam(sd, arch, inputs_embeds: Tensor, *, num_beams: int, max_new_to
         sc = top_lp / ((cur + 1) ** length_penalty)
         sc = sc + (~unsat)[:, None].float() * -1.0e9 + (~did).float() * -1.0e9
         m_sc, sel = torch.topk(torch.cat([beam_score, sc], 1), nb)
+        if trace is not None:
+            was, old_fin = unsat.clone(), fin.clone()
+            mg = [gaps(torch.topk(lp[b], K + 1)[0].tolist()) +
+                  gaps(torch.topk(torch.cat([beam_score[b], sc[b]]), nb + 1)[0].tolist()) for b in range(B)]
         seqs, beam_idx = take(torch.cat([seqs, t_seq], 1), sel), take(torch.cat([beam_idx, t_bidx], 1), sel)
         fin, beam_score = take(torch.cat([fin, did], 1), sel), m_sc
         cache.reorder(run_bidx[:, :, cur].reshape(-1))
         best_running = run_score[:, 0] / ((cur + 1) ** length_penalty)
         worst = torch.where(fin, beam_score.min(dim=1, keepdim=True)[0], torch.full_like(beam_score, -1.0e9))
         unsat = unsat & (best_running[:, None] > worst).any(dim=1)
+        if trace is not None:
+            trace["steps"] = cur + 1
+            for b in range(B):
+                if not bool(was[b]):
+                    continue
+                ev = trace["events"][b]
+                ev["did"] += int(did[b].sum())
+                ev["late"] += int(((tok[b] == eos) & (torch.arange(K) >= nb)).sum())
+                ev["evict"] += int(old_fin[b].sum()) - int((fin[b] & (sel[b] < nb)).sum())
+                ev["best_replaced"] += int(bool(old_fin[b].any()) and int(sel[b, 0]) >= nb)
+                if bool(fin[b].any()) and float(beam_score[b].min()) > -1.0e8:
+                    mg[b].append(abs(float(best_running[b]) - float(beam_score[b].min())))
+                trace["margins"][b].append(min(mg[b]) if mg[b] else float("inf"))
+                if not bool(unsat[b]):
+                    trace["sat_step"][b] = cur
         if not bool(unsat.any()) or bool(hits.all()):
             break
         logits = gpt2_forward(sd, arch, wte[run_seq[:, :, cur].reshape(-1)].unsqueeze(1), cache)[:, -1, :].float()
-    n = int((beam_idx[:, 0, :] != -1).sum(dim=1).max())
+    lens = (beam_idx[:, 0, :] != -1).sum(dim=1)
+    n = int(lens.max())
+    if trace is not None:
+        trace.update(lengths=lens.tolist(), stopped_early=trace["steps"] < L)
     return seqs[:, 0, :n].tolist()
 
 

@@ -219,3 +219,32 @@ def test_oracle_hypothesis_scores_match_reference_beam_scores(name, nb):
     with torch.no_grad():
         got = O.hypothesis_scores(sd, ga, x, g[f"beam{nb}_ids"].tolist())
     np.testing.assert_allclose(got, g[f"beam{nb}_scores"], rtol=0, atol=2e-5)
+
+
+def _beam_eos_names():
+    import beam_cases as BC
+    return list(BC.GOLDEN_CASES)
+
+
+@pytest.mark.parametrize("name", _beam_eos_names())
+def test_oracle_beam_matches_transformers_eos_rich(name):
+    """EOS-rich searches (tests/beam_cases.py): the oracle's restatement on the float32 weights equals
+    what transformers' own GPT2LMHeadModel.generate returned (tests/golden/beam_eos, make_goldens.py
+    beam_eos_case) - ids, width and each hypothesis' length.  The reference's clips never finish a
+    hypothesis, so this is what pins the finished-beam half of the restatement to HF; the float64
+    oracle of the case table gives the same rows wherever the table calls a row certain."""
+    import beam_cases as BC
+    meta, g = golden("beam_eos")
+    c = BC.BY_NAME[name]
+    rec = meta["cases"][name]
+    assert {k: (list(v) if isinstance(v, tuple) else v) for k, v in c._asdict().items()} == \
+        {k: rec[k] for k in c._fields}, "beam_cases.py changed: regenerate tests/golden/beam_eos"
+    rows, tr = BC.run_oracle(c, f32=True)
+    exp, lens = g[f"{name}_ids"], g[f"{name}_lengths"]
+    print(f"\nbeam-eos {name}: HF lengths {lens.tolist()} oracle {tr['lengths']}", end="")
+    assert np.array_equal(np.array(rows, dtype=np.int32), exp), (rows, exp.tolist())
+    assert tr["lengths"] == lens.tolist()
+    rows64, tr64 = BC.oracle(name)
+    for b, listed in enumerate(BC.listed_certain(c)):
+        if listed:
+            assert tr64["lengths"][b] == lens[b] and rows64[b][:lens[b]] == exp[b, :lens[b]].tolist(), (name, b)
