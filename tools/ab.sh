@@ -5,6 +5,8 @@
 # runner: bench   python bench.py (quick leg: no CPU baseline / host e2e / parity / decode-alone)
 #         gemm    tools/gemm_bench.py        (ViT GEMM shapes alone)
 #         attn    tools/attn_bench.py        (ViT attention alone; BT from the environment)
+#         qkv     tools/qkv_attn_bench.py    (fused QKV + attention against the unfused pair; BT / NT / H /
+#                                            DTYPES from the environment)
 #         decode  tools/decode_step_time.py  (decode step alone; B from the environment)
 # spec:   "<ENV=V ...>|<args>"  - environment (e.g. VCAP_LIB=<path to a variant build>, made with
 #         VCAP_LIB_NAME / VCAP_EXTRA_FLAGS through vcap.build or tools/build_ref_lib.sh) and
@@ -15,6 +17,7 @@ case $runner in
   bench)  cmd="python bench.py --cpu-baseline-s 0 --host-e2e 0 --no-parity --no-decode-alone --strict-steps 0 --token-exact-steps 0" ;;
   gemm)   cmd="python tools/gemm_bench.py" ;;
   attn)   cmd="python tools/attn_bench.py" ;;
+  qkv)    cmd="python tools/qkv_attn_bench.py" ;;
   decode) cmd="python tools/decode_step_time.py" ;;
   *) echo "unknown runner $runner"; exit 2 ;;
 esac

@@ -33,13 +33,10 @@ def bench(dname):
     s = torch.cuda.current_stream().cuda_stream
     lib = N.lib()
 
-    def unfused(cls_only=0):
+    def unfused():
         N.check(lib.vcap_gemm(dt, dt, xn.data_ptr(), D, w.data_ptr(), D, qkv.data_ptr(), 3 * D, BT * NT,
                               3 * D, D, b.data_ptr(), 0, None, 0, 0, 0, 0, 0, 0, s), "qkv gemm")
-        if cls_only:
-            N.check(lib.vcap_vit_attention(dt, qkv.data_ptr(), ref.data_ptr(), BT, NT, H, s), "attn")
-        else:
-            N.check(lib.vcap_vit_attention(dt, qkv.data_ptr(), ref.data_ptr(), BT, NT, H, s), "attn")
+        N.check(lib.vcap_vit_attention(dt, qkv.data_ptr(), ref.data_ptr(), BT, NT, H, s), "attn")
 
     def fused(cls_only=0):
         N.check(lib.vcap_vit_qkv_attention_dt(dt, xn.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), BT, NT, H,

@@ -56,8 +56,6 @@ struct Carver {
   }
 };
 
-bool attn_lds_configured = false;
-
 // Decoder rows one call may carry (B * (prefix + prompt) at the prefill, rows of a step).  Rows go
 // through the GEMV kernels in 16 / 32-row chunks (blockIdx.y), so this bounds workspace sizes only.
 constexpr int kMaxDecodeRows = 512;
@@ -803,16 +801,9 @@ int vcap_jpeg_decode_batch(const uint8_t* const* data, const size_t* lens, int n
   return 0;
 }
 
-static int ensure_attn_lds() {
-  if (attn_lds_configured) return 0;
-  attn_lds_configured = true;
-  return 0;
-}
-
 int vcap_vit_attention(int dtype, const void* qkv, void* out, int frames, int tokens, int heads, void* stream) {
   if (!qkv || !out || frames <= 0 || tokens <= 0 || heads <= 0) return fail(VCAP_E_ARG, "vcap_vit_attention: bad arguments");
   if (tokens > 288) return fail(VCAP_E_UNSUPPORTED, "vcap_vit_attention: tokens > 288");
-  ensure_attn_lds();
   VCAP_TRY(vcap_vit_attention_dispatch(dtype, qkv, out, frames, tokens, heads, (hipStream_t)stream),
            "vcap_vit_attention");
   return 0;

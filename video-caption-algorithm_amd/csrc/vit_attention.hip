@@ -17,8 +17,35 @@
 #include "vcap_common.h"
 #include "vcap_kernels.h"
 
+// Every kernel of this file takes its LDS as dynamic shared memory, most of them above the 64 KiB that
+// need the explicit opt-in: set once per process and kernel instantiation, then launch.
+template <auto Kernel, typename... Args>
+static hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static bool configured = false;
+  if (!configured) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    configured = true;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+
 // cls_only: compute the class-token query (q = 0) of each (frame, head) only and write it to
 // compact row `frame` of out (the last block of the encoder: only CLS rows are consumed after it).
+// The one statement of that rule, for every kernel of this file: lane row fr of query tile qt of
+// frame bt holds query q; it is stored when `keep`, to row `row` of out.
+struct AttnRow {
+  int q;
+  bool keep;
+  long row;
+};
+
+VCAP_DEV AttnRow attn_out_row(int qt, int fr, int N, int cls_only, int bt) {
+  const int q = qt * 16 + fr;
+  return {q, q < N && (!cls_only || q == 0), cls_only ? (long)bt : (long)bt * N + q};
+}
+
 template <typename T, int KT>
 __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                  int N, int H, int cls_only) {
@@ -70,7 +97,7 @@ __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __rest
   const int qtiles = cls_only ? 1 : (N + 15) / 16;
   const float scale = 0.125f;  // 64^-0.5
   for (int qt = wave; qt < qtiles; qt += 4) {
-    int q = qt * 16 + fr;
+    const int q = qt * 16 + fr;
     const int qc = q < N ? q : N - 1;
     u32x4 qf[NS];
 #pragma unroll
@@ -143,8 +170,11 @@ __global__ __launch_bounds__(256) void vcap_vit_attention_kernel(const T* __rest
         }
       }
     }
-    if (q < N && (!cls_only || q == 0)) {
-      T* orow = out + (cls_only ? (long)bt : (long)bt * N + q) * D + h * 64;
+    // the row rule is asked here, not up at the Q loads: asked there, every instantiation compiles to another
+    // schedule (profiles/vit_attention_refactor_resources.txt)
+    const AttnRow r = attn_out_row(qt, fr, N, cls_only, bt);
+    if (r.keep) {
+      T* orow = out + r.row * D + h * 64;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         const f32x4 v = o[dt] * inv;  // O^T[d = dt*16 + 4*fg + r][q]
@@ -183,9 +213,6 @@ VCAP_DEV void glds16_attn(const void* g, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
-
-template <typename T>
-VCAP_DEV uint32_t cvt_pk16(float lo, float hi) { return Pack2<T>::pack(lo, hi); }
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
@@ -261,9 +288,9 @@ VCAP_DEV void attn_bf16_qtile(const char* Ks, const char* Vs, const u32x4 (&qf)[
   const int qr = fr >> 2, p4 = fr & 3;
 #pragma unroll
   for (int c = 0; c < KT / 2; ++c) {
-    const u32x4 pf = (u32x4){cvt_pk16<T>(st[2 * c][0], st[2 * c][1]), cvt_pk16<T>(st[2 * c][2], st[2 * c][3]),
-                             cvt_pk16<T>(st[2 * c + 1][0], st[2 * c + 1][1]),
-                             cvt_pk16<T>(st[2 * c + 1][2], st[2 * c + 1][3])};
+    const u32x4 pf = (u32x4){Pack2<T>::pack(st[2 * c][0], st[2 * c][1]), Pack2<T>::pack(st[2 * c][2], st[2 * c][3]),
+                             Pack2<T>::pack(st[2 * c + 1][0], st[2 * c + 1][1]),
+                             Pack2<T>::pack(st[2 * c + 1][2], st[2 * c + 1][3])};
     const int r0 = 32 * c + 4 * fg + qr, r1 = r0 + 16;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -291,11 +318,11 @@ struct AttnOut {
 };
 
 template <bool MXO, typename T>
-VCAP_DEV AttnOut attn_pack(const f32x4 (&o)[4], float inv, long row, bool keep) {
+VCAP_DEV AttnOut attn_pack(const f32x4 (&o)[4], float inv, const AttnRow& to) {
   const int lane = threadIdx.x & 63;
   AttnOut r;
-  r.row = row;
-  r.keep = keep;
+  r.row = to.row;
+  r.keep = to.keep;
   r.sb0 = r.sb1 = 0;
   if constexpr (MXO) {
     // block b = dims [32b, 32b+32) of the row: dt in {2b, 2b+1} of this lane and lanes fg = 0..3;
@@ -326,8 +353,8 @@ VCAP_DEV AttnOut attn_pack(const f32x4 (&o)[4], float inv, long row, bool keep) 
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const f32x4 va = o[2 * k] * inv, vb = o[2 * k + 1] * inv;
-      const uint32_t a0 = cvt_pk16<T>(va.x, va.y), a1 = cvt_pk16<T>(va.z, va.w);
-      const uint32_t b0 = cvt_pk16<T>(vb.x, vb.y), b1 = cvt_pk16<T>(vb.z, vb.w);
+      const uint32_t a0 = Pack2<T>::pack(va.x, va.y), a1 = Pack2<T>::pack(va.z, va.w);
+      const uint32_t b0 = Pack2<T>::pack(vb.x, vb.y), b1 = Pack2<T>::pack(vb.z, vb.w);
       const uint32_t r0 = (uint32_t)xor16_i((int)(odd ? a0 : b0));
       const uint32_t r1 = (uint32_t)xor16_i((int)(odd ? a1 : b1));
       const u32x4 w = odd ? (u32x4){r0, r1, b0, b1} : (u32x4){a0, a1, r0, r1};
@@ -368,7 +395,6 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
                                                                              uint8_t* __restrict__ oscale,
                                                                              int groups, int cls_only) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NP = KT * 16;
   constexpr int NS = KE * 16;  // staged key rows (the all-padding last tile is never read)
   constexpr int QT_MAX = (KT + WAVES - 1) / WAVES;  // query tiles per wave (N <= NP)
   static_assert(KT % 2 == 0, "PV consumes 32-key chunks");
@@ -392,7 +418,6 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
     glds16_attn(src + D, Ks + blk * 1024);
     glds16_attn(src + 2 * D, Vs + blk * 1024);
   }
-  (void)NP;
   // ---- this wave's Q fragments
   const int qtiles = cls_only ? 1 : (N + 15) / 16;
   u32x4 qf[QT_MAX][2];
@@ -412,10 +437,7 @@ __global__ __launch_bounds__(WAVES * 64) void vcap_vit_attention_bf16_kernel(con
     f32x4 o[4];
     float inv;
     attn_bf16_qtile<KT, KE, T>(Ks, Vs, qf[i], N, o, inv);
-    const int q = qt * 16 + fr;
-    const bool keep = q < N && (!cls_only || q == 0);
-    const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<MXO>(attn_pack<MXO, T>(o, inv, row, keep), out, D, h, oscale, groups);
+    attn_commit<MXO>(attn_pack<MXO, T>(o, inv, attn_out_row(qt, fr, N, cls_only, bt)), out, D, h, oscale, groups);
   }
 }
 
@@ -423,17 +445,9 @@ template <int KT, int KE, int WAVES, bool MXO, typename T>
 static hipError_t launch_attn_bf16(const void* qkv, void* out, int BT, int N, int H, uint8_t* oscale, int cls_only,
                                    hipStream_t s) {
   const size_t lds = (size_t)KE * 16 * 128 * 2;  // 53 KiB at KE = 13: three workgroups per CU
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO, T>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
   const int groups = ((cls_only ? BT : BT * N) + 255) / 256;  // scale rows = output rows
-  hipLaunchKernelGGL((vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO, T>), dim3(BT * H), dim3(WAVES * 64), lds, s,
-                     (const T*)qkv, out, N, H, oscale, groups, cls_only);
-  return hipGetLastError();
+  return launch_dyn_lds<vcap_vit_attention_bf16_kernel<KT, KE, WAVES, MXO, T>>(
+      dim3(BT * H), dim3(WAVES * 64), lds, s, (const T*)qkv, out, N, H, oscale, groups, cls_only);
 }
 
 template <typename T, int KT>
@@ -441,16 +455,8 @@ static hipError_t launch_attn(const void* qkv, void* out, int BT, int N, int H, 
   constexpr int NP = KT * 16;
   constexpr int VS = NP + (sizeof(T) == 2 ? 8 : 4);
   const size_t lds = (size_t)NP * 64 * sizeof(T) + (size_t)64 * VS * sizeof(T);
-  static bool configured = false;  // dynamic LDS above 64 KiB needs the explicit opt-in
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_attention_kernel<T, KT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  hipLaunchKernelGGL((vcap_vit_attention_kernel<T, KT>), dim3(BT * H), dim3(256), lds, s, (const T*)qkv, (T*)out, N,
-                     H, cls_only);
-  return hipGetLastError();
+  return launch_dyn_lds<vcap_vit_attention_kernel<T, KT>>(dim3(BT * H), dim3(256), lds, s, (const T*)qkv, (T*)out, N,
+                                                          H, cls_only);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -503,17 +509,15 @@ VCAP_DEV void qa_wait_older(bool older) {
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __restrict__ xn,
-                                                                     const T* __restrict__ wqkv,
-                                                                     const float* __restrict__ bqkv,
-                                                                     T* __restrict__ out, int BT, int N, int H,
-                                                                     int cls_only) {
-  using namespace qa;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int D = H * 64;  // = K of the projection
-  const int b = blockIdx.x;
-  int bt, h;
+// ---- What the two fused kernels below share: everything but how K-tiles reach LDS.  TW = token tiles
+// of a wave's token group (7 of 13, 9 of 17), RT = token rows.  Wave `wave` owns feature tiles
+// 3 fgrp .. 3 fgrp + 2 (fgrp = wave & 3) and the ntt <= TW token tiles from t0 on; (fr, fg) = (lane & 15,
+// lane >> 4), computed once by the kernel (computed inside each helper, the L kernel's staging compiled
+// to another block layout).  One copy each, so the arithmetic, K order, bias add and rounding of the two
+// kernels cannot drift apart.
+
+// (frame, head) of workgroup b: XCD-aware when frames % 8 == 0 (see the grid note above)
+VCAP_DEV void qkv_frame_head(int b, int BT, int H, int& bt, int& h) {
   if ((BT & 7) == 0) {
     const int x = b & 7, j = b >> 3;
     bt = (j / H) * 8 + x;
@@ -522,11 +526,109 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __
     bt = b / H;
     h = b - bt * H;
   }
+}
+
+// this wave's fragments of one K-tile: token rows at Tb, weight rows at Wb (the L kernel keeps these reads
+// written out, see there: keep the two in step)
+template <int TW>
+VCAP_DEV void qkv_read_frags(const char* Tb, const char* Wb, int fr, int fg, int fgrp, int t0, int ntt,
+                             u32x4 (&wf)[2][3], u32x4 (&tf)[2][TW]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int row = (fgrp * 3 + i) * 16 + fr;
+      wf[s][i] = *reinterpret_cast<const u32x4*>(Wb + row * 128 + (((s * 4 + fg) ^ (row & 7)) << 4));
+    }
+#pragma unroll
+    for (int j = 0; j < TW; ++j) {
+      if (j < ntt) {
+        const int row = (t0 + j) * 16 + fr;
+        tf[s][j] = *reinterpret_cast<const u32x4*>(Tb + row * 128 + (((s * 4 + fg) ^ (row & 7)) << 4));
+      }
+    }
+  }
+}
+
+// the MFMA phase of one K-tile
+template <int TW, typename T>
+VCAP_DEV void qkv_mfma(const u32x4 (&wf)[2][3], const u32x4 (&tf)[2][TW], int ntt, f32x4 (&acc)[3][TW]) {
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int j = 0; j < TW; ++j)
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (j < ntt) acc[i][j] = mfma_frag(wf[s][i], tf[s][j], acc[i][j], (T*)nullptr);
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// The ring's first 3 RT rows become the K, V and Q images ([token][64], chunk ^ (token & 7)): bias add,
+// rounding to T, and the barrier after which any wave may read them.
+template <int TW, int RT, typename T>
+VCAP_DEV void qkv_write_images(char* smem, const f32x4 (&acc)[3][TW], const float* __restrict__ bqkv, int D, int h,
+                               int fr, int fg, int fgrp, int t0, int ntt) {
+  char* Ks = smem;
+  char* Vs = smem + RT * 128;
+  char* Qs = smem + 2 * RT * 128;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int ft = fgrp * 3 + i, part = ft >> 2;        // 0 q, 1 k, 2 v
+    const int d0 = (ft & 3) * 16 + 4 * fg;              // this lane's 4 features of the head
+    const f32x4 bias = *reinterpret_cast<const f32x4*>(bqkv + part * D + h * 64 + d0);
+    char* img = part == 0 ? Qs : (part == 1 ? Ks : Vs);
+#pragma unroll
+    for (int j = 0; j < TW; ++j) {
+      if (j < ntt) {
+        const int tok = (t0 + j) * 16 + fr;
+        const f32x4 v = acc[i][j] + bias;
+        const u32x2 p = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
+        *reinterpret_cast<u32x2*>(img + tok * 128 + (((d0 >> 3) ^ (tok & 7)) << 4) + (d0 & 7) * 2) = p;
+      }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the images written before any wave reads them
+  qa_barrier();
+}
+
+// One query tile on the images: attn_bf16_qtile and the store.  The loop over a wave's query tiles
+// stays in the kernels: lifted in here, hipcc no longer unrolls it (ds_read_b128 132 -> 64 and VGPRs
+// 234 -> 254 in the L kernel).
+template <int KT, int KE, int RT, typename T>
+VCAP_DEV void qkv_attend_tile(const char* smem, int qt, int fr, int fg, int N, int cls_only, int bt, int D, int h,
+                              T* out) {
+  const char* Ks = smem;
+  const char* Vs = smem + RT * 128;
+  const char* Qs = smem + 2 * RT * 128;
+  u32x4 qf[2];
+  const int qrow = qt * 16 + fr;  // rows past N hold row N - 1's q (clamped staging)
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    qf[s] = *reinterpret_cast<const u32x4*>(Qs + qrow * 128 + (((s * 4 + fg) ^ (qrow & 7)) << 4));
+  f32x4 o[4];
+  float inv;
+  attn_bf16_qtile<KT, KE, T>(Ks, Vs, qf, N, o, inv);
+  attn_commit<false>(attn_pack<false, T>(o, inv, attn_out_row(qt, fr, N, cls_only, bt)), out, D, h, nullptr, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __restrict__ xn,
+                                                                     const T* __restrict__ wqkv,
+                                                                     const float* __restrict__ bqkv,
+                                                                     T* __restrict__ out, int BT, int N, int H,
+                                                                     int cls_only) {
+  using namespace qa;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int TW = 7;   // token tiles per wave: groups of 7 / 6
+  const int D = H * 64;  // = K of the projection
+  int bt, h;
+  qkv_frame_head(blockIdx.x, BT, H, bt, h);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int fgrp = wave & 3, tgrp = wave >> 2;
-  const int t0 = tgrp * 7, ntt = tgrp ? TT - 7 : 7;
+  const int t0 = tgrp * TW, ntt = tgrp ? TT - TW : TW;
 
   // The two wave groups (tgrp 0 = waves 0-3, one per SIMD, token tiles 0-6; tgrp 1 = waves 4-7,
   // tiles 7-12) run one barrier apart: while one group issues its 42 MFMAs of a K-tile the other
@@ -562,11 +664,11 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __
     else qa_wait_older<false>(older);
   };
 
-  f32x4 acc[3][7];
+  f32x4 acc[3][TW];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 7; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < TW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int nk = D / 64;
   stage(0);
@@ -579,62 +681,18 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __
     // of K-tile kt - 1, whose reads both groups finished before the last barrier)
     const char* Tb = smem + (kt % NSTAGE) * STAGE;
     const char* Wb = Tb + RT * 128;
-    u32x4 wf[2][3], tf[2][7];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int row = (fgrp * 3 + i) * 16 + fr;
-        wf[s][i] = *reinterpret_cast<const u32x4*>(Wb + row * 128 + (((s * 4 + fg) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        if (j < ntt) {
-          const int row = (t0 + j) * 16 + fr;
-          tf[s][j] = *reinterpret_cast<const u32x4*>(Tb + row * 128 + (((s * 4 + fg) ^ (row & 7)) << 4));
-        }
-      }
-    }
+    u32x4 wf[2][3], tf[2][TW];
+    qkv_read_frags<TW>(Tb, Wb, fr, fg, fgrp, t0, ntt, wf, tf);
     if (kt + 2 < nk) stage(kt + 2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers before the barrier
     wait_tile(kt + 2 < nk);                             // this wave's pieces of K-tile kt + 1 landed
     qa_barrier();
-    // ---- MFMA phase
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 7; ++j)
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          if (j < ntt) acc[i][j] = mfma_frag(wf[s][i], tf[s][j], acc[i][j], (T*)nullptr);
-    __builtin_amdgcn_s_setprio(0);
+    qkv_mfma<TW, T>(wf, tf, ntt, acc);
     qa_barrier();
   }
   if (tgrp == 0) qa_barrier();       // balance group 1's extra barrier
   qa_barrier();                      // every wave's fragment reads done: the ring becomes the images
-
-  char* Ks = smem;
-  char* Vs = smem + RT * 128;
-  char* Qs = smem + 2 * RT * 128;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int ft = fgrp * 3 + i, part = ft >> 2;        // 0 q, 1 k, 2 v
-    const int d0 = (ft & 3) * 16 + 4 * fg;              // this lane's 4 features of the head
-    const f32x4 bias = *reinterpret_cast<const f32x4*>(bqkv + part * D + h * 64 + d0);
-    char* img = part == 0 ? Qs : (part == 1 ? Ks : Vs);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      if (j < ntt) {
-        const int tok = (t0 + j) * 16 + fr;
-        const f32x4 v = acc[i][j] + bias;
-        const u32x2 p = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
-        *reinterpret_cast<u32x2*>(img + tok * 128 + (((d0 >> 3) ^ (tok & 7)) << 4) + (d0 & 7) * 2) = p;
-      }
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the images written before any wave reads them
-  qa_barrier();
+  qkv_write_images<TW, RT, T>(smem, acc, bqkv, D, h, fr, fg, fgrp, t0, ntt);
 
   constexpr int WAVES = 8, QT_MAX = 2;
   const int qtiles = cls_only ? 1 : (N + 15) / 16;
@@ -642,18 +700,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_kernel(const T* __
   for (int i = 0; i < QT_MAX; ++i) {
     const int qt = wave + i * WAVES;
     if (qt >= qtiles) break;
-    u32x4 qf[2];
-    const int qrow = qt * 16 + fr;  // rows past N hold row N - 1's q (clamped staging)
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-      qf[s] = *reinterpret_cast<const u32x4*>(Qs + qrow * 128 + (((s * 4 + fg) ^ (qrow & 7)) << 4));
-    f32x4 o[4];
-    float inv;
-    attn_bf16_qtile<14, 13, T>(Ks, Vs, qf, N, o, inv);
-    const int q = qt * 16 + fr;
-    const bool keep = q < N && (!cls_only || q == 0);
-    const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<false>(attn_pack<false, T>(o, inv, row, keep), out, D, h, nullptr, 0);
+    qkv_attend_tile<14, 13, RT, T>(smem, qt, fr, fg, N, cls_only, bt, D, h, out);
   }
 }
 
@@ -703,22 +750,15 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
                                                                        int cls_only) {
   using namespace qb;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int TW = 9;  // token tiles per wave: groups of 9 / 8
   const int D = H * 64;
-  const int b = blockIdx.x;
   int bt, h;
-  if ((BT & 7) == 0) {
-    const int x = b & 7, j = b >> 3;
-    bt = (j / H) * 8 + x;
-    h = j - (j / H) * H;
-  } else {
-    bt = b / H;
-    h = b - bt * H;
-  }
+  qkv_frame_head(blockIdx.x, BT, H, bt, h);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int fgrp = wave & 3, tgrp = wave >> 2;
-  const int t0 = tgrp * 9, ntt = tgrp ? TT - 9 : 9;
+  const int t0 = tgrp * TW, ntt = tgrp ? TT - TW : TW;
   char* const Tsl = smem;                     // token slots
   char* const Wsl = smem + NTS * TSLOT;       // weight slots
 
@@ -760,11 +800,11 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
       if (i >= nw && i < npc) glds16_attn(src[i] + kt * 128, dst + dsto[i]);
   };
 
-  f32x4 acc[3][9];
+  f32x4 acc[3][TW];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 9; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < TW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int nk = D / 64;
   stage_w(0);
@@ -778,7 +818,10 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
     // kt - 1, read by both groups before the last barrier), every wave its token pieces of kt + 2
     const char* Tb = Tsl + (kt % NTS) * TSLOT;
     const char* Wb = Wsl + (kt % NWS) * WSLOT;
-    u32x4 wf[2][3], tf[2][9];
+    // qkv_read_frags<TW>, written out: through the helper this kernel compiles to another read / MFMA
+    // schedule that measured 1 % slower (bf16 128.3 against 127.3 us, f16 132.9 against 131.4 at 64 frames
+    // x 16 heads; with the reads written out 127.0 and 130.9: profiles/vit_attention_refactor_ab.txt)
+    u32x4 wf[2][3], tf[2][TW];
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
@@ -787,7 +830,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
         wf[s2][i] = *reinterpret_cast<const u32x4*>(Wb + row * 128 + (((s2 * 4 + fg) ^ (row & 7)) << 4));
       }
 #pragma unroll
-      for (int j = 0; j < 9; ++j) {
+      for (int j = 0; j < TW; ++j) {
         if (j < ntt) {
           const int row = (t0 + j) * 16 + fr;
           tf[s2][j] = *reinterpret_cast<const u32x4*>(Tb + row * 128 + (((s2 * 4 + fg) ^ (row & 7)) << 4));
@@ -800,43 +843,13 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers before the barrier
     qb_vm_wait(w_now + t_now);                          // all but this phase's pieces: tokens of kt + 1
     qa_barrier();
-    // ---- MFMA phase
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int j = 0; j < 9; ++j)
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          if (j < ntt) acc[i][j] = mfma_frag(wf[s2][i], tf[s2][j], acc[i][j], (T*)nullptr);
-    __builtin_amdgcn_s_setprio(0);
+    qkv_mfma<TW, T>(wf, tf, ntt, acc);
     if (w_now) qb_vm_wait(t_now);  // group 0: the weights of kt + 1 landed before group 1 reads them
     qa_barrier();
   }
   if (tgrp == 0) qa_barrier();       // balance group 1's extra barrier
   qa_barrier();                      // every wave's fragment reads done: the token slots become the images
-
-  char* Ks = smem;
-  char* Vs = smem + RT * 128;
-  char* Qs = smem + 2 * RT * 128;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int ft = fgrp * 3 + i, part = ft >> 2;        // 0 q, 1 k, 2 v
-    const int d0 = (ft & 3) * 16 + 4 * fg;
-    const f32x4 bias = *reinterpret_cast<const f32x4*>(bqkv + part * D + h * 64 + d0);
-    char* img = part == 0 ? Qs : (part == 1 ? Ks : Vs);
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      if (j < ntt) {
-        const int tok = (t0 + j) * 16 + fr;
-        const f32x4 v = acc[i][j] + bias;
-        const u32x2 pk = (u32x2){Pack2<T>::pack(v.x, v.y), Pack2<T>::pack(v.z, v.w)};
-        *reinterpret_cast<u32x2*>(img + tok * 128 + (((d0 >> 3) ^ (tok & 7)) << 4) + (d0 & 7) * 2) = pk;
-      }
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  qa_barrier();
+  qkv_write_images<TW, RT, T>(smem, acc, bqkv, D, h, fr, fg, fgrp, t0, ntt);
 
   constexpr int WAVES = 8, QT_MAX = 3;
   const int qtiles = cls_only ? 1 : (N + 15) / 16;
@@ -844,18 +857,7 @@ __global__ __launch_bounds__(512) void vcap_vit_qkv_attention_l_kernel(const T* 
   for (int i = 0; i < QT_MAX; ++i) {
     const int qt = wave + i * WAVES;
     if (qt >= qtiles) break;
-    u32x4 qf[2];
-    const int qrow = qt * 16 + fr;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-      qf[s2] = *reinterpret_cast<const u32x4*>(Qs + qrow * 128 + (((s2 * 4 + fg) ^ (qrow & 7)) << 4));
-    f32x4 o[4];
-    float inv;
-    attn_bf16_qtile<18, 17, T>(Ks, Vs, qf, N, o, inv);
-    const int q = qt * 16 + fr;
-    const bool keep = q < N && (!cls_only || q == 0);
-    const long row = cls_only ? (long)bt : (long)bt * N + q;
-    attn_commit<false>(attn_pack<false, T>(o, inv, row, keep), out, D, h, nullptr, 0);
+    qkv_attend_tile<18, 17, RT, T>(smem, qt, fr, fg, N, cls_only, bt, D, h, out);
   }
 }
 
@@ -867,28 +869,11 @@ bool vcap_vit_qkv_attention_supported(int dt, int N, int H) {
 template <typename T>
 static hipError_t launch_qkv_attention(const void* xn, const void* wqkv, const float* bqkv, void* out, int BT, int N,
                                        int H, int cls_only, hipStream_t s) {
-  if (N > 13 * 16) {  // ViT-L/14: 17 token tiles
-    static bool configured_l = false;
-    if (!configured_l) {
-      hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_l_kernel<T>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, qb::LDS);
-      if (e != hipSuccess) return e;
-      configured_l = true;
-    }
-    hipLaunchKernelGGL(vcap_vit_qkv_attention_l_kernel<T>, dim3(BT * H), dim3(512), qb::LDS, s, (const T*)xn,
-                       (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
-    return hipGetLastError();
-  }
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)vcap_vit_qkv_attention_kernel<T>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, qa::LDS);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  hipLaunchKernelGGL(vcap_vit_qkv_attention_kernel<T>, dim3(BT * H), dim3(512), qa::LDS, s, (const T*)xn,
-                     (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
-  return hipGetLastError();
+  if (N > 13 * 16)  // ViT-L/14: 17 token tiles
+    return launch_dyn_lds<vcap_vit_qkv_attention_l_kernel<T>>(dim3(BT * H), dim3(512), qb::LDS, s, (const T*)xn,
+                                                              (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
+  return launch_dyn_lds<vcap_vit_qkv_attention_kernel<T>>(dim3(BT * H), dim3(512), qa::LDS, s, (const T*)xn,
+                                                          (const T*)wqkv, bqkv, (T*)out, BT, N, H, cls_only);
 }
 
 hipError_t vcap_vit_qkv_attention_dispatch(int dt, const void* xn, const void* wqkv, const float* bqkv, void* out,
@@ -914,28 +899,33 @@ static hipError_t attn_bf16_dispatch(const void* qkv, void* out, uint8_t* oscale
   }
 }
 
+// generic kernel of element type T at the first key-tile count of the list that holds kt tiles
+template <typename T, int KT, int... MORE>
+static hipError_t attn_generic_dispatch(int kt, const void* qkv, void* out, int BT, int N, int H, int cls_only,
+                                        hipStream_t s) {
+  if (kt <= KT) return launch_attn<T, KT>(qkv, out, BT, N, H, cls_only, s);
+  if constexpr (sizeof...(MORE) > 0) return attn_generic_dispatch<T, MORE...>(kt, qkv, out, BT, N, H, cls_only, s);
+  return hipErrorInvalidValue;
+}
+
+// Kernel by (dtype, N), with kt = 2 ceil(N / 32) key tiles (keys padded to a multiple of 32); the ViT
+// frame windows are kt = 2 (N <= 32), 14 (193..224) and 18 (257..288):
+//   dtype  in a window                                           elsewhere (N <= 256)
+//   bf16   vcap_vit_attention_bf16_kernel<kt, KE, 4 or 8 waves>  invalid
+//   f16    the same kernel (the 2-byte schedule)                 vcap_vit_attention_kernel<f16, 4 | 8 | 12 | 16>
+//   f32    vcap_vit_attention_kernel<float, kt>                  invalid
+// KE = kt - 1 when the last key tile is all padding (N <= 208, N <= 272), else kt; the f16 generic kernel
+// pads the keys to 64 / 128 / 192 / 256 and masks.  Any other dtype, N <= 0 and N > 288 are invalid.
 hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int BT, int N, int H, hipStream_t s,
                                        int cls_only) {
   if (N <= 0 || N > 288) return hipErrorInvalidValue;
+  const int kt = ((N + 31) / 32) * 2;
+  const bool window = kt == 2 || kt == 14 || kt == 18;
   if (dt == VCAP_DT_BF16) return attn_bf16_dispatch<false, bf16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
-  if (dt == VCAP_DT_F16) {
-    // the ViT frame sizes run the bf16 path's schedule; any other token count the generic kernel
-    // (keys padded to 64 / 128 / 192 / 256 and masked)
-    const int kt = ((N + 31) / 32) * 2;
-    if (kt == 2 || kt == 14 || kt == 18)
-      return attn_bf16_dispatch<false, f16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
-    if (kt <= 4) return launch_attn<f16_t, 4>(qkv, out, BT, N, H, cls_only, s);
-    if (kt <= 8) return launch_attn<f16_t, 8>(qkv, out, BT, N, H, cls_only, s);
-    if (kt <= 12) return launch_attn<f16_t, 12>(qkv, out, BT, N, H, cls_only, s);
-    return launch_attn<f16_t, 16>(qkv, out, BT, N, H, cls_only, s);
-  }
-  if (dt != VCAP_DT_F32) return hipErrorInvalidValue;
-  switch (((N + 31) / 32) * 2) {
-    case 2: return launch_attn<float, 2>(qkv, out, BT, N, H, cls_only, s);
-    case 14: return launch_attn<float, 14>(qkv, out, BT, N, H, cls_only, s);
-    case 18: return launch_attn<float, 18>(qkv, out, BT, N, H, cls_only, s);
-    default: return hipErrorInvalidValue;
-  }
+  if (dt == VCAP_DT_F16 && window) return attn_bf16_dispatch<false, f16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
+  if (dt == VCAP_DT_F16) return attn_generic_dispatch<f16_t, 4, 8, 12, 16>(kt, qkv, out, BT, N, H, cls_only, s);
+  if (dt == VCAP_DT_F32 && window) return attn_generic_dispatch<float, 2, 14, 18>(kt, qkv, out, BT, N, H, cls_only, s);
+  return hipErrorInvalidValue;
 }
 
 // bf16 q/k/v -> MXFP8 attention output (+ scales) for the MXFP8 attn-proj GEMM
