@@ -347,6 +347,33 @@ int vcap_gpt2_reorder(const vcap_gpt2_desc* d, const int* src_rows, int rows, in
 int vcap_gpt2_forward_embeds(const vcap_gpt2_desc* d, const float* embeds, int rows, int n_tok, int past_len, int S0,
                              int max_new_tokens, float* logits_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- teacher-forced scoring (added within ABI v16: two new symbols, nothing else changes): one forward
+ *      over B sequences of S input embeddings with logits, target log-probs and the LM loss at EVERY
+ *      position - GPT2TextDecoder.forward / VideoCaptionModel.forward / compute_loss of the reference
+ *      (src/models/text_decoder.py:76-103, src/models/caption_model.py:83-91, 104-168), forward pass
+ *      only.  All pointers are device memory.
+ *        embeds      [B, S, E] f32 inputs_embeds; h = embeds + wpe[0..S): positions are 0..S-1 whatever
+ *                    the mask holds, as HF's GPT2LMHeadModel(inputs_embeds=, attention_mask=) forward
+ *                    does (pinned by tests/golden/score_tiny.npz, the reference's own output)
+ *        key_mask    [B, S] bytes or NULL (all ones): query i of sequence b attends to the keys j <= i
+ *                    with key_mask[b][j] != 0.  PRECONDITION: key_mask[b][0] != 0 (the reference always
+ *                    prepends ones for the prefix, so no row is ever fully masked).  It is checked on the
+ *                    device, without a host synchronisation: every logprob_out entry of an offending
+ *                    sequence is NaN, and loss_out[0] with them if one of its positions is counted (callers holding the mask on the host check it
+ *                    there: vcap.model.HipGPT2Decoder.score raises VCAP_E_ARG)
+ *        targets     [B, S] or NULL: the token to predict AT position i (already shifted: the caller does
+ *                    HF's logits[:, :-1] vs labels[:, 1:]); -100 (any value outside [0, vocab)) = ignored
+ *        logits_out  [B, S, vocab] f32 or NULL (not stored then)
+ *        logprob_out [B, S] f32 or NULL: log_softmax(logits[b, i])[targets[b, i]], 0 where ignored
+ *        loss_out    [2] f32 or NULL: {sum of -logprob over the counted positions, their count}
+ *      Limits: B * S <= vcap_gpt2_max_rows() and S <= n_positions (VCAP_E_UNSUPPORTED otherwise); both
+ *      decoder dtypes.  Deterministic: fixed reduction orders, no float atomics, so two calls on the same
+ *      inputs give the same bits.  The call leaves no KV state and is not graph-captured. ---- */
+size_t vcap_gpt2_score_workspace_bytes(const vcap_gpt2_desc* d, int B, int S);
+int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
+                    const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
+                    size_t ws_bytes, void* stream);
+
 /* ---- live kernel timing for the benchmark's roofline (sites: "vit.qkv", "vit.attention",
  *      "vit.proj", "vit.fc1", "vit.fc2"): events are recorded around each launch of the site on
  *      the caller's stream, without synchronising; vcap_probe_read waits for them. ---- */

@@ -336,9 +336,25 @@ VCAP_DEV void c64_issue(C64Loads<T>& L, const T* q, const T* kc, const T* vc, in
   }
 }
 
-// s_q / s_p: this wave's 64 floats each of LDS (s_q 16-byte aligned); orow = out + m * E + h * 64
+// Optional per-sequence key mask of the attention kernels (teacher-forced scoring: vcap_gpt2_score).
+// A hidden key's score is -inf before the softmax.  KeyMask<false> is empty and hides nothing, so the
+// unmasked instantiations are today's kernels.  Key 0 of every sequence must be visible (a row with no
+// visible key has no softmax).
+template <bool MASKED>
+struct KeyMask {
+  VCAP_DEV bool hidden(int, int) const { return false; }
+};
+template <>
+struct KeyMask<true> {
+  const uint8_t* m;  // [seqs][ld]: 0 = key hidden from every query of its sequence
+  int ld;
+  VCAP_DEV bool hidden(int seq, int j) const { return m[(long)seq * ld + j] == 0; }
+};
+
+// s_q / s_p: this wave's 64 floats each of LDS (s_q 16-byte aligned); orow = out + m * E + h * 64;
+// vis: key `lane` is not hidden by a key mask
 template <typename T>
-VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, T* orow) {
+VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, T* orow, bool vis = true) {
   constexpr int E8 = C64Loads<T>::E8, NK = C64Loads<T>::NK, NV = C64Loads<T>::NV;
   const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
   float f[E8];
@@ -356,7 +372,7 @@ VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, 
     for (int e = 0; e < E8; ++e) sc += s_q[c * E8 + e] * f[e];
   }
   sc *= 0.125f;
-  const bool live = lane < ctx;
+  const bool live = lane < ctx && vis;
   const float mx = wave_max(live ? sc : -INFINITY);
   const float p = live ? __expf(sc - mx) : 0.f;
   const float sum = wave_sum(p);
@@ -870,12 +886,12 @@ __global__ __launch_bounds__(256) void vcap_rows_gemm_lds_kernel(RowsGemmArgs a)
 // broadcast with ds_bpermute, so no K/V load waits on a dependent page-table load.
 // Scores: lane j <-> key j (+64 ...), full 64-dim dot.  P.V: lane = (key group kg of 8, 8
 // consecutive dims d8), partial sums reduced over the 8 key groups by DPP + permlane swaps.
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __restrict__ q, const T* __restrict__ kc,
                                                                     const T* __restrict__ vc,
                                                                     const int* __restrict__ page_table, int maxp,
                                                                     T* __restrict__ out, int M, int H, int S_new,
-                                                                    int past) {
+                                                                    int past, KeyMask<MASKED> km) {
   constexpr int E8 = Frag<T>::kElems;  // elements per 16-byte chunk
   __shared__ float s_q[4][64];
   __shared__ float s_p[4][1024];
@@ -906,6 +922,8 @@ __global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __r
     }
     s *= 0.125f;
     if (j0 + lane < ctx) {
+      if constexpr (MASKED)
+        if (km.hidden(seq, j0 + lane)) s = -INFINITY;
       s_p[wave][j0 + lane] = s;
       mx = fmaxf(mx, s);
     }
@@ -1728,11 +1746,11 @@ size_t vcap_rows_packed_size(int dt, int N, int K) {
 // page table): page ids are computed, not loaded, and q, the lane's K row and all of its V rows
 // are issued together, so the wave pays ONE memory round trip instead of three
 // (page table -> K -> V).  Arithmetic identical to vcap_decode_attention_kernel.
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(64) void vcap_decode_attention_c64_kernel(const T* __restrict__ q, const T* __restrict__ kc,
                                                                        const T* __restrict__ vc, int maxp,
                                                                        T* __restrict__ out, int M, int H, int S_new,
-                                                                       int past) {
+                                                                       int past, KeyMask<MASKED> km) {
   __shared__ __attribute__((aligned(16))) float s_q[64];
   __shared__ float s_p[64];
   const int item = blockIdx.x;  // one 64-thread workgroup per (row, head)
@@ -1742,32 +1760,46 @@ __global__ __launch_bounds__(64) void vcap_decode_attention_c64_kernel(const T* 
   const int ctx = qpos + 1;  // <= 64 (dispatcher)
   C64Loads<T> L;
   c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);
-  c64_finish<T>(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64);
+  bool vis = true;
+  if constexpr (MASKED) vis = !km.hidden(seq, min((int)threadIdx.x, ctx - 1));
+  c64_finish<T>(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64, vis);
 }
 
-hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
-                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s) {
-  if (past + S_new > 1024 || maxp > 64) return hipErrorInvalidValue;
+template <bool MASKED>
+static hipError_t launch_decode_attention(int dt, const void* q, const void* kc, const void* vc, const int* pt, int maxp,
+                                          void* out, int M, int H, int S_new, int past, hipStream_t s,
+                                          KeyMask<MASKED> km) {
   const dim3 grid((M * H + 3) / 4), block(256);
   if (!pt && past + S_new <= 64 && (dt == VCAP_DT_BF16 || dt == VCAP_DT_F32)) {
     // one 64-thread workgroup per (row, head): the ~100-200 items of a decode step spread over as
     // many CUs (each item's q / K / V round trip on a CU of its own) instead of 4 per CU
     if (dt == VCAP_DT_BF16)
-      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<bf16_t>), dim3(M * H), dim3(64), 0, s, (const bf16_t*)q,
-                         (const bf16_t*)kc, (const bf16_t*)vc, maxp, (bf16_t*)out, M, H, S_new, past);
+      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<bf16_t, MASKED>), dim3(M * H), dim3(64), 0, s,
+                         (const bf16_t*)q, (const bf16_t*)kc, (const bf16_t*)vc, maxp, (bf16_t*)out, M, H, S_new, past,
+                         km);
     else
-      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<float>), dim3(M * H), dim3(64), 0, s, (const float*)q,
-                         (const float*)kc, (const float*)vc, maxp, (float*)out, M, H, S_new, past);
+      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<float, MASKED>), dim3(M * H), dim3(64), 0, s,
+                         (const float*)q, (const float*)kc, (const float*)vc, maxp, (float*)out, M, H, S_new, past, km);
     return hipGetLastError();
   }
   if (!pt) return hipErrorInvalidValue;  // the general kernels read the page table
   if (dt == VCAP_DT_BF16)
-    hipLaunchKernelGGL((vcap_decode_attention_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)q,
-                       (const bf16_t*)kc, (const bf16_t*)vc, pt, maxp, (bf16_t*)out, M, H, S_new, past);
+    hipLaunchKernelGGL((vcap_decode_attention_kernel<bf16_t, MASKED>), grid, block, 0, s, (const bf16_t*)q,
+                       (const bf16_t*)kc, (const bf16_t*)vc, pt, maxp, (bf16_t*)out, M, H, S_new, past, km);
   else
-    hipLaunchKernelGGL((vcap_decode_attention_kernel<float>), grid, block, 0, s, (const float*)q, (const float*)kc,
-                       (const float*)vc, pt, maxp, (float*)out, M, H, S_new, past);
+    hipLaunchKernelGGL((vcap_decode_attention_kernel<float, MASKED>), grid, block, 0, s, (const float*)q,
+                       (const float*)kc, (const float*)vc, pt, maxp, (float*)out, M, H, S_new, past, km);
   return hipGetLastError();
+}
+
+// kmask [seqs][mask_ld] (optional): the masked instantiations of the same two kernels
+hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
+                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s,
+                                          const uint8_t* kmask, int mask_ld) {
+  if (past + S_new > 1024 || maxp > 64) return hipErrorInvalidValue;
+  if (!kmask) return launch_decode_attention(dt, q, kc, vc, pt, maxp, out, M, H, S_new, past, s, KeyMask<false>{});
+  if (mask_ld < past + S_new) return hipErrorInvalidValue;
+  return launch_decode_attention(dt, q, kc, vc, pt, maxp, out, M, H, S_new, past, s, KeyMask<true>{kmask, mask_ld});
 }
 
 hipError_t vcap_prefill_embed_dispatch(int dt, const float* prefix, int P, const int* ids, int nids, const void* wte,

@@ -14,42 +14,11 @@
 // bf16 / f16 use mfma_f32_16x16x32_bf16 / _f16 (f16: the reference's autocast dtype, rounded where
 // autocast rounds: Autocast<T> in vcap_common.h); the fp32 parity mode uses mfma_f32_16x16x4f32 with the
 // SAME byte layout (one 16-byte chunk = 4 f32 = one group of four 16x16x4 MFMAs).
+#include "gemm_tile.h"
 #include "vcap_common.h"
 #include "vcap_kernels.h"
 
-namespace {
-
-constexpr int BM = 128, BN = 128, ROWB = 128;  // ROWB: bytes of K per tile row
-constexpr int TILE_BYTES = BM * ROWB;          // 16 KiB per operand per stage
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;
-
-VCAP_DEV void glds16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <typename T>
-VCAP_DEV void stage_tile(const T* __restrict__ P, long ld, int row0, int rows, int k0, char* lds_tile,
-                         int wave, int lane) {
-  constexpr int E = Frag<T>::kElems;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int rb = wave * 4 + i;              // 8-row block written by this wave instruction
-    const int r = rb * 8 + (lane >> 3);
-    const int s = lane & 7;                   // LDS slot within the 128-byte row
-    const int c = s ^ (r & 7);                // global chunk stored in that slot
-    int gr = row0 + r;
-    gr = gr < rows ? gr : rows - 1;
-    const T* src = P + (long)gr * ld + k0 + c * E;
-    glds16(src, lds_tile + rb * 1024);
-  }
-}
-
-VCAP_DEV u32x4 lds_frag(const char* tile, int row, int chunk) {
-  return *reinterpret_cast<const u32x4*>(tile + row * ROWB + ((chunk ^ (row & 7)) << 4));
-}
-
-}  // namespace
+using namespace gemm_tile;
 
 // EPI (compile time, so each ViT GEMM role is its own kernel symbol in a profile):
 //   0 bias (QKV)   1 bias+gelu_tanh (fc1)   2 bias+residual in place (attn-proj, fc2)
@@ -59,7 +28,6 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
                                                         const TIn* __restrict__ W, long ldw,
                                                         TOut* C, long ldc, int M, int N, int K, GemmEpi epi) {
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_BYTES];
-  constexpr int E = Frag<TIn>::kElems;
   constexpr int BK = ROWB / sizeof(TIn);
 
   const int tiles_n = (N + BN - 1) / BN;
@@ -88,39 +56,8 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
   const int nk = K / BK / (int)gridDim.y;
   const int kt0 = (int)blockIdx.y * nk;
   const bool split = gridDim.y > 1;
-  stage_tile(A, lda, m0, M, kt0 * BK, smem, wave, lane);
-  stage_tile(W, ldw, n0, N, kt0 * BK, smem + TILE_BYTES, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
+  tile_loop(A, lda, W, ldw, m0, M, n0, N, kt0, nk, smem, acc);
   const int fr = lane & 15, fg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    char* cur = smem + (kt & 1) * STAGE_BYTES;
-    if (kt + 1 < nk) {
-      char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
-      stage_tile(A, lda, m0, M, (kt0 + kt + 1) * BK, nxt, wave, lane);
-      stage_tile(W, ldw, n0, N, (kt0 + kt + 1) * BK, nxt + TILE_BYTES, wave, lane);
-    }
-    const char* ta = cur;
-    const char* tb = cur + TILE_BYTES;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      u32x4 af[4], bfr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = lds_frag(ta, wm * 64 + i * 16 + fr, s * 4 + fg);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfr[j] = lds_frag(tb, wn * 64 + j * 16 + fr, s * 4 + fg);
-      // weight fragment as the MFMA A operand: a lane ends up with 4 consecutive COLUMNS of
-      // one row, so the epilogue stores vectors
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma_frag(bfr[j], af[i], acc[i][j], (TIn*)nullptr);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  (void)E;
 
   // epilogue: lane holds row fr, columns 4*fg .. 4*fg+3 of each 16x16 tile
   const bool vec = (N & 3) == 0 && (ldc & 3) == 0 && (!epi.res || (epi.ldr & 3) == 0);

@@ -240,7 +240,8 @@ int check_gpt2_launch(const vcap_gpt2_desc* d) {
 }
 
 int run_layers(const vcap_gpt2_desc* d, const DecBufs& w, int maxp, size_t page_elems, int M, int S_new, int past,
-               int max_blocks, hipStream_t s, const int* anc = nullptr, int anc_ld = 0) {
+               int max_blocks, hipStream_t s, const int* anc = nullptr, int anc_ld = 0,
+               const uint8_t* kmask = nullptr, int mask_ld = 0) {
   const int E = d->n_embd, H = d->n_head, L = d->n_layer;
   const int dt = d->dtype;
   const size_t es = esize(dt);
@@ -267,8 +268,9 @@ int run_layers(const vcap_gpt2_desc* d, const DecBufs& w, int maxp, size_t page_
     if (anc)   // beam search: keys through the ancestry table (one query row per sequence)
       VCAP_TRY(vcap_decode_attention_anc_dispatch(dt, w.q, a.kc, a.vc, anc, anc_ld, maxp, w.attn, M, H, past, s),
                "decode_attention_anc");
-    else
-      VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, pt_arg, maxp, w.attn, M, H, S_new, past, s),
+    else   // kmask (teacher-forced scoring): keys hidden per sequence on top of the causal order
+      VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, pt_arg, maxp, w.attn, M, H, S_new, past, s, kmask,
+                                              mask_ld),
                "decode_attention");
     // 3) attn c_proj + residual
     RowsGemmArgs b;
@@ -1225,6 +1227,69 @@ int vcap_gpt2_forward_embeds(const vcap_gpt2_desc* d, const float* embeds, int r
   if (int rc = run_layers(d, w, maxp, pe, rows * n_tok, n_tok, past_len, 0, s)) return rc;
   int nblk;
   return run_lm_head(d, w, rows, n_tok, logits_out, 1, 0, 1.0f, 0, -1, &nblk, s);
+}
+
+// ---- teacher-forced scoring: the decode state (carve_dec; the paged cache is scratch here) for B
+// sequences of S positions, then the all-rows lm_head's operand and partials
+struct ScoreBufs {
+  DecBufs w;
+  int maxp;
+  size_t pe;
+  void* xn;        // [B*S][E] ln_f rows, decoder dtype
+  float* pmax;     // [B*S][nparts]
+  float* psum;
+  float* tlogit;   // [B*S]
+  float* logprob;  // [B*S]
+  int nparts;
+};
+
+static ScoreBufs carve_score(Carver& c, const vcap_gpt2_desc* d, int B, int S) {
+  ScoreBufs b;
+  b.w = carve_dec(c, d, B, S, 1, &b.maxp, &b.pe);
+  const size_t M = (size_t)B * S;
+  b.nparts = vcap_score_parts(d->vocab);
+  b.xn = c.take(M * d->n_embd * esize(d->dtype));
+  b.pmax = (float*)c.take(M * b.nparts * 4);
+  b.psum = (float*)c.take(M * b.nparts * 4);
+  b.tlogit = (float*)c.take(M * 4);
+  b.logprob = (float*)c.take(M * 4);
+  return b;
+}
+
+size_t vcap_gpt2_score_workspace_bytes(const vcap_gpt2_desc* d, int B, int S) {
+  if (check_gpt2(d) || B <= 0 || S <= 0 || d->vocab <= 0) return 0;
+  Carver c(nullptr);
+  carve_score(c, d, B, S);
+  return c.off;
+}
+
+int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
+                    const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
+                    size_t ws_bytes, void* stream) {
+  if (int rc = check_gpt2_launch(d)) return rc;
+  if (!embeds || B <= 0 || S <= 0 || !workspace) return fail(VCAP_E_ARG, "vcap_gpt2_score: bad arguments");
+  if (!logits_out && !targets) return fail(VCAP_E_ARG, "vcap_gpt2_score: neither logits_out nor targets given");
+  if ((logprob_out || loss_out) && !targets)
+    return fail(VCAP_E_ARG, "vcap_gpt2_score: logprob_out / loss_out need targets");
+  if ((long)B * S > kMaxDecodeRows) return fail(VCAP_E_UNSUPPORTED, "B*S exceeds vcap_gpt2_max_rows()");
+  if (S > d->n_positions) return fail(VCAP_E_UNSUPPORTED, "S exceeds n_positions");
+  if (ws_bytes < vcap_gpt2_score_workspace_bytes(d, B, S))
+    return fail(VCAP_E_WORKSPACE, "vcap_gpt2_score: workspace too small (vcap_gpt2_score_workspace_bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace);
+  const ScoreBufs b = carve_score(c, d, B, S);
+  const DecBufs& w = b.w;
+  const int M = B * S, E = d->n_embd;
+  VCAP_TRY(vcap_decode_init_dispatch(w.pt, B, b.maxp, w.finished, w.nbanned, s, w.skc, w.n_skc), "decode_init");
+  // the prefill-embedding kernel with every position taken from `embeds`: h = embeds + wpe[0..S)
+  VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, embeds, S, nullptr, 0, d->wte, d->wpe, w.h, B, E, s), "embed_inputs");
+  if (int rc = run_layers(d, w, b.maxp, b.pe, M, S, 0, 0, s, nullptr, 0, key_mask, S)) return rc;
+  VCAP_TRY(vcap_layernorm_dispatch(d->dtype, w.h, E, b.xn, E, d->lnf_g, d->lnf_b, M, E, d->ln_eps, s), "ln_f");
+  ScoreLmArgs a{b.xn, d->wte, M, d->vocab, E, targets, logits_out, b.pmax, b.psum, b.tlogit, b.nparts};
+  VCAP_TRY(vcap_score_lm_dispatch(d->dtype, a, s), "score_lm_head");
+  if (targets)
+    VCAP_TRY(vcap_score_combine_dispatch(a, key_mask, S, b.logprob, logprob_out, loss_out, s), "score_combine");
+  return 0;
 }
 
 int vcap_gpt2_reorder(const vcap_gpt2_desc* d, const int* src_rows, int rows, int S0, int max_new_tokens, int length,

@@ -150,8 +150,30 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
 hipError_t vcap_rows_pack_dispatch(int dt, const void* w, long ldw, int N, int K, void* packed, hipStream_t s);
 size_t vcap_rows_packed_size(int dt, int N, int K);
 int vcap_logit_blocks(int V, int M);
+// kmask (optional) [seqs][mask_ld] bytes: key j of a sequence with kmask[seq][j] == 0 is hidden from every
+// query of that sequence (score -inf before the softmax); key 0 must be visible
 hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
-                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s);
+                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s,
+                                          const uint8_t* kmask = nullptr, int mask_ld = 0);
+// ---- teacher-forced scoring (csrc/score.hip): lm_head + cross-entropy over every row ----
+struct ScoreLmArgs {
+  const void* xn;       // [M][E] ln_f rows in the decoder dtype
+  const void* wte;      // [V][E] tied lm_head, plain row-major (vcap_gpt2_desc.wte)
+  int M, V, E;
+  const int* targets;   // [M] or nullptr: token to predict at the row; outside [0, V) = ignored
+  float* logits;        // [M][V] or nullptr
+  float* part_max;      // [M][nparts]: per 64-column part, max and sum exp(x - max) of the row's logits
+  float* part_sum;
+  float* tgt_logit;     // [M]: the target's logit (written by the one part that holds its column)
+  int nparts;           // vcap_score_parts(V)
+};
+int vcap_score_parts(int V);
+hipError_t vcap_score_lm_dispatch(int dt, const ScoreLmArgs& a, hipStream_t s);
+// log-prob of each row's target from the parts, in part order (0 where ignored; NaN for every row of a
+// sequence whose key_mask[seq][0] is 0) -> logprob_ws [M] and, optional, logprob_out [M]; then, optional,
+// loss_out = {sum of -logprob over the counted rows in row order, their count}
+hipError_t vcap_score_combine_dispatch(const ScoreLmArgs& a, const uint8_t* kmask, int S, float* logprob_ws,
+                                       float* logprob_out, float* loss_out, hipStream_t s);
 hipError_t vcap_prefill_embed_dispatch(int dt, const float* prefix, int P, const int* ids, int nids, const void* wte,
                                        const float* wpe, float* h, int B, int E, hipStream_t s, int pos0 = 0,
                                        int prefix_rep = 1);

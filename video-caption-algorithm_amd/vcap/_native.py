@@ -128,6 +128,8 @@ SIGNATURES = {
     "vcap_gpt2_step": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "vcap_gpt2_reorder": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, i32, i32, vp, sz, vp]),
     "vcap_gpt2_forward_embeds": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "vcap_gpt2_score_workspace_bytes": (sz, [C.POINTER(GPT2Desc), i32, i32]),
+    "vcap_gpt2_score": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "vcap_probe_enable": (i32, [C.c_char_p, i32]),
     "vcap_probe_read": (i32, [C.c_char_p, fp, C.POINTER(C.c_int)]),
     "vcap_probe_read_launches": (i32, [C.c_char_p, fp, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]),

@@ -147,6 +147,46 @@ class HipTextDecoder:
     def prefix_embeds(self, emb: torch.Tensor) -> torch.Tensor:
         return self.mapper_op.project(emb)
 
+    def token_embeds(self, ids: torch.Tensor) -> torch.Tensor:
+        """wte rows [.., E] f32 of the decoder's own table: the rows its generate() feeds back."""
+        return self.hip.wte[ids.to(self.hip.device).long()].float()
+
+    @torch.no_grad()
+    def forward_from_prefix(self, prefix: torch.Tensor, input_ids: torch.Tensor,
+                            attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                            want_logits: bool = True):
+        """GPT2TextDecoder.forward after the mapper: prefix [B, P, E] -> vcap.model.ScoreResult over the
+        P + L positions (one vcap_gpt2_score pass per chunk of sequences)."""
+        dev = self.hip.device
+        B, P = prefix.shape[0], prefix.shape[1]
+        ids = input_ids.to(dev).long()
+        if attention_mask is None:
+            attention_mask = ids != self.tokenizer.pad_token_id
+        att = attention_mask.to(dev) != 0
+        if ids.shape[0] == 1 and B > 1:        # _build_inputs expands a batch-1 prompt
+            ids, att = ids.expand(B, -1), att.expand(B, -1)
+        x = torch.cat([prefix.to(dev, torch.float32), self.token_embeds(ids)], dim=1)
+        km = torch.cat([torch.ones(B, P, dtype=torch.bool, device=dev), att], dim=1)
+        targets = None
+        if labels is not None:
+            # HF shifts inside the model: the logits at position i are scored against label i + 1
+            ext = torch.cat([torch.full((B, P), -100, dtype=torch.long, device=dev), labels.to(dev).long()], dim=1)
+            targets = torch.cat([ext[:, 1:], torch.full((B, 1), -100, dtype=torch.long, device=dev)], dim=1)
+        return self.hip.score(x, km, targets, want_logits=want_logits, check_mask=P == 0)
+
+    @torch.no_grad()
+    def forward(self, video_emb: torch.Tensor, input_ids: torch.Tensor,
+                attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+        """GPT2TextDecoder.forward (text_decoder.py:76-103), forward pass only: inputs = mapper prefix ‖
+        wte[input_ids]; attention_mask defaults to input_ids != pad, ones prepended for the prefix; labels
+        get -100 for the prefix.  -> {"loss": 0-dim f32 (nll_sum / count; NaN with nothing counted) or
+        None, "logits": [B, P + L, V] f32}."""
+        r = self.forward_from_prefix(self.prefix_embeds(video_emb.to(self.hip.device)), input_ids, attention_mask,
+                                     labels)
+        return {"loss": r.loss, "logits": r.logits}
+
+    __call__ = forward
+
     def generate_from_prefix(self, prefix: torch.Tensor, prompt_ids: Sequence[int], *, max_new_tokens: int = 32,
                              num_beams: int = 1, temperature: float = 1.0, top_p: float = 0.9,
                              no_repeat_ngram_size: int = 3, repetition_penalty: float = 1.15,
@@ -224,6 +264,53 @@ class HipVideoCaptionModel:
         """VideoCaptionModel.generate (caption_model.py:93-101): encoder -> proj -> decoder.generate."""
         emb = self.proj(self.encoder(video.to(self.device)))
         return self.decoder.generate(emb, prompt=prompt, **gen_kwargs)
+
+    @torch.no_grad()
+    def forward(self, video: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                labels: Optional[torch.Tensor] = None):
+        """VideoCaptionModel.forward (caption_model.py:83-91): encoder -> proj -> decoder.forward."""
+        emb = self.proj(self.encoder(video.to(self.device)))
+        return self.decoder(emb, input_ids, attention_mask, labels)
+
+    __call__ = forward
+
+    @torch.no_grad()
+    def compute_loss(self, video: torch.Tensor, caption_ids: torch.Tensor, pad_id: int) -> torch.Tensor:
+        """VideoCaptionModel.compute_loss (caption_model.py:104-168), forward pass only: caption_ids
+        [B, L] = <bos> ... <eos>, right-padded with pad_id.  As there, the key mask is
+        `caption_ids[:, :-1] != pad_id` - with bos = eos = pad (GPT-2) that also hides the leading BOS -
+        and the labels at pad positions are NOT ignored."""
+        emb = self.proj(self.encoder(video.to(self.device)))
+        prefix = self.decoder.prefix_embeds(emb)
+        ids = caption_ids.to(self.device).long()
+        inp, labels = ids[:, :-1], ids[:, 1:]
+        return self.decoder.forward_from_prefix(prefix, inp, inp != pad_id, labels, want_logits=False).loss
+
+    @torch.no_grad()
+    def score_ids(self, video: torch.Tensor, ids: Sequence[Sequence[int]], *, ln_scale: float = 0.6,
+                  in_weight: float = 0.4):
+        """Log-likelihood of B generated token lists (no prompt; the prompt is BOS, as generate_ids'
+        default) under the engine's prefix path: -> (logprobs f32 [B, Lmax], 0 past each length;
+        lengths int64 [B]; sums f32 [B]), on the device.  logprobs[b, k] = log p(ids[b][k] | video b,
+        BOS, ids[b][:k]).  One pass, no logits stored: the fast path for reranking candidates."""
+        _, prefix = self.encode_prefix(video, ln_scale, in_weight)
+        B, P = prefix.shape[0], prefix.shape[1]
+        if len(ids) != B:
+            raise ValueError(f"{len(ids)} token lists for {B} videos")
+        eos = self.gpt2_arch.eos_token_id
+        lens = [len(r) for r in ids]
+        L = max(max(lens), 1)
+        tok = torch.full((B, L), eos, dtype=torch.long)
+        tgt = torch.full((B, P + L), -100, dtype=torch.long)
+        for b, r in enumerate(ids):
+            row = torch.tensor([int(t) for t in r], dtype=torch.long)
+            tok[b, :lens[b]] = row
+            tgt[b, P:P + lens[b]] = row       # position P holds BOS and predicts ids[b][0]
+        tok = tok.to(self.device)
+        bos = torch.full((B, 1), self.gpt2_arch.bos_token_id, dtype=torch.long, device=self.device)
+        x = torch.cat([prefix.float(), self.decoder.token_embeds(torch.cat([bos, tok[:, :-1]], dim=1))], dim=1)
+        lp = self.decoder.hip.score(x, None, tgt, want_logits=False).logprobs[:, P:]
+        return lp, torch.tensor(lens, device=self.device), lp.sum(dim=1)
 
     @torch.no_grad()
     def generate_ids(self, video: torch.Tensor, prompt_ids: Sequence[int], *, ln_scale: float = 0.6,

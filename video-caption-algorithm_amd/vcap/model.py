@@ -240,6 +240,20 @@ class GenConfig:
         return cls(max_new_tokens, 0, 0, 1.0, eos, eos, use_graph)
 
 
+@dataclass
+class ScoreResult:
+    """HipGPT2Decoder.score's outputs (device tensors; None where not requested)."""
+    logits: Optional[torch.Tensor]     # [B, S, V] f32
+    logprobs: Optional[torch.Tensor]   # [B, S] f32: log p(targets[b, i] | inputs up to i), 0 where ignored
+    nll_sum: Optional[torch.Tensor]    # 0-dim f32: sum of -logprob over the counted positions
+    count: Optional[torch.Tensor]      # 0-dim f32: how many positions were counted
+
+    @property
+    def loss(self) -> Optional[torch.Tensor]:
+        """Mean cross-entropy (NaN with no counted position, as F.cross_entropy gives)."""
+        return None if self.nll_sum is None else self.nll_sum / self.count
+
+
 class HipGPT2Decoder:
     """GPT2LMHeadModel greedy generate from inputs_embeds (text_decoder.py:131-144) on the HIP path."""
 
@@ -393,6 +407,65 @@ class HipGPT2Decoder:
                                            _stream(prefix.device)), "vcap_gpt2_generate")
         return out
 
+
+    @torch.no_grad()
+    def score(self, embeds: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
+              targets: Optional[torch.Tensor] = None, want_logits: bool = False,
+              check_mask: bool = True) -> "ScoreResult":
+        """Teacher-forced forward over embeds [B, S, E] (inputs_embeds: prefix + token embeddings), one
+        vcap_gpt2_score call per chunk of sequences with B_chunk * S <= vcap_gpt2_max_rows().
+
+        key_mask [B, S] (nonzero = visible): query i attends to the visible keys j <= i; positions stay
+        0..S-1.  Column 0 must be visible: checked here (one small device read) unless the caller built
+        the mask with ones in front itself and passes check_mask=False.  targets [B, S]: the token to
+        predict at each position (already shifted), -100 = ignored.  Returns logits [B, S, V] when
+        want_logits, logprobs [B, S] (0 where ignored) and the (nll_sum, count) pair when targets are
+        given - the chunks' pairs added in chunk order - all on the device."""
+        x = embeds.to(self.device, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] != self.arch.n_embd:
+            raise ValueError(f"embeds shape {tuple(x.shape)} != [B, S, {self.arch.n_embd}]")
+        B, S, _ = x.shape
+        V = self.arch.vocab
+        max_rows = int(N.lib().vcap_gpt2_max_rows())
+        if B < 1 or S < 1 or S > max_rows or S > self.arch.n_positions:
+            raise N.VcapError(f"score: S = {S} exceeds vcap_gpt2_max_rows() = {max_rows} or n_positions",
+                              N.E_UNSUPPORTED)
+        if targets is None and not want_logits:
+            raise ValueError("score: give targets, want_logits, or both")
+        km = tg = logits = logprobs = None
+        if key_mask is not None:
+            km = (key_mask != 0).to(self.device, torch.uint8).contiguous()
+            if tuple(km.shape) != (B, S):
+                raise ValueError(f"key_mask shape {tuple(km.shape)} != {(B, S)}")
+            if check_mask and not bool(km[:, 0].all()):
+                raise N.VcapError("score: key_mask[:, 0] must be nonzero (a row with no visible key)", N.E_ARG)
+        if targets is not None:
+            tg = targets.to(self.device, torch.int32).contiguous()
+            if tuple(tg.shape) != (B, S):
+                raise ValueError(f"targets shape {tuple(tg.shape)} != {(B, S)}")
+            logprobs = torch.empty(B, S, dtype=torch.float32, device=self.device)
+        if want_logits:
+            logits = torch.empty(B, S, V, dtype=torch.float32, device=self.device)
+        per = max(1, max_rows // S)
+        starts = list(range(0, B, per))
+        pairs = torch.empty(len(starts), 2, dtype=torch.float32, device=self.device) if tg is not None else None
+        stream = _stream(self.device)
+        for ci, b0 in enumerate(starts):
+            nb = min(per, B - b0)
+            ws = self.ws.get(int(N.lib().vcap_gpt2_score_workspace_bytes(C.byref(self.desc), nb, S)))
+            N.check(N.lib().vcap_gpt2_score(C.byref(self.desc), x[b0:].data_ptr(), nb, S,
+                                            N.ptr(None if km is None else km[b0:]),
+                                            N.ptr(None if tg is None else tg[b0:]),
+                                            N.ptr(None if logits is None else logits[b0:]),
+                                            N.ptr(None if logprobs is None else logprobs[b0:]),
+                                            N.ptr(None if pairs is None else pairs[ci]),
+                                            ws.data_ptr(), ws.numel(), stream), "vcap_gpt2_score")
+        nll_sum = count = None
+        if pairs is not None:
+            nll_sum, count = pairs[0, 0], pairs[0, 1]
+            for ci in range(1, len(starts)):   # chunk order: the same sum on every run
+                nll_sum, count = nll_sum + pairs[ci, 0], count + pairs[ci, 1]
+        return ScoreResult(logits, logprobs, nll_sum, count)
 
     def _beam_ids(self, prefix, prompt_ids, cfg: GenConfig, out, workspace, lengths_out):
         B, P, E = prefix.shape
