@@ -129,7 +129,7 @@ def patch_attention(s: str) -> str:
 def main():
     tmp = Path("/tmp/vcap_stamps_build")
     shutil.rmtree(tmp, ignore_errors=True)
-    src = tmp / "pkg" / "csrc"  # runtime.hip includes ../../include/vcap.h
+    src = tmp / "pkg" / "csrc"  # runtime_common.h includes ../../include/vcap.h
     src.mkdir(parents=True)
     (tmp / "obj").mkdir()
     shutil.copytree(ROOT / "include", tmp / "include")

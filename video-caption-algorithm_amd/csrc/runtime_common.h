@@ -1,0 +1,82 @@
+// Private to the host runtime behind the C ABI (runtime.hip, runtime_vit.hip, runtime_gpt2.hip,
+// graph_cache.hip): the error plumbing, workspace carving, the probe scope and the graph cache's interface.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <functional>
+#include <string>
+
+#include "../../include/vcap.h"
+#include "vcap_common.h"
+#include "vcap_kernels.h"
+
+extern thread_local std::string vcap_err;   // what vcap_last_error() returns (defined in runtime.hip)
+
+inline int fail(int code, const std::string& msg) {
+  vcap_err = msg;
+  return code;
+}
+
+inline int hip_fail(hipError_t e, const char* where) {
+  if (e == hipSuccess) return 0;
+  vcap_err = std::string(where) + ": " + hipGetErrorString(e);
+  return -(int)e;
+}
+
+#define VCAP_TRY(expr, where)                    \
+  do {                                           \
+    hipError_t _e = (expr);                      \
+    if (_e != hipSuccess) return hip_fail(_e, where); \
+  } while (0)
+
+inline size_t esize(int dt) { return vcap_dt_size(dt); }
+inline size_t mx_scale_bytes(int rows, int K) { return (size_t)(K / 128) * (size_t)((rows + 255) / 256) * 1024; }
+inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
+
+// Hands out 256-byte-aligned pieces of a workspace; over a null base it only adds up, so a size query
+// and the launch that carves the same buffers cannot disagree.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  void* take(size_t bytes) {
+    void* p = base ? base + off : nullptr;
+    off += al(bytes);
+    return p;
+  }
+};
+
+// what a workspace query returns: the bytes `carve(Carver&)` takes
+template <typename F>
+size_t carved_bytes(F carve) {
+  Carver c(nullptr);
+  carve(c);
+  return c.off;
+}
+
+// Times one launch of a probed site (runtime.hip: vcap_probe_enable / vcap_probe_read*): HIP events
+// recorded around it on the caller's stream, no synchronisation.  `site` is read in the constructor only.
+struct Probe;
+struct ProbeScope {
+  Probe* p;
+  hipStream_t s;
+  int idx;
+  ProbeScope(const char* site, hipStream_t st, int rows);
+  ~ProbeScope();
+};
+
+// ---- graph_cache.hip
+// Bytes of everything a captured decode bakes in; two calls replay one graph only if their keys are equal.
+struct GraphKey {
+  std::string k;
+  explicit GraphKey(const char* tag = "") : k(tag) {}
+  void put(const void* p, size_t n) { k.append((const char*)p, n); }
+  template <typename T>
+  void val(const T& v) { put(&v, sizeof(v)); }
+  void put_desc(const vcap_gpt2_desc* d);   // the descriptor without its tail padding, then every layer
+  void put_device();                        // the current device
+};
+
+// Replay the graph cached under `key` on s, capturing `issue(capture_stream)` into it first if absent.
+int launch_cached(const std::string& key, hipStream_t s, const std::function<int(hipStream_t)>& issue);

@@ -61,7 +61,7 @@ class HipViTEncoder:
     def __init__(self, sd: Dict[str, np.ndarray], arch: ViTArch, precision: str = "bf16", device="cuda",
                  video_dim: int = VIDEO_DIM, mx_gemms: Sequence[str] = MX_GEMMS):
         """precision "fp8": the block GEMMs named in `mx_gemms` run in MXFP8, the others in bf16
-        (their weights bf16, their scales NULL in the descriptor: csrc/runtime.hip picks per GEMM)."""
+        (their weights bf16, their scales NULL in the descriptor: csrc/runtime_vit.hip picks per GEMM)."""
         N.lib()
         self.arch, self.precision, self.device = arch, precision, torch.device(device)
         if precision not in _VIT_DTYPES:
@@ -263,7 +263,7 @@ class HipGPT2Decoder:
     # the rescoring's fma chain, n_embd <= 1024 terms) add 2 x 1024 x 2^-24 each, doubled for an
     # accumulator that truncates (2.44e-4): 8.07e-3, and 1.6 % over it.  The runtime multiplies the
     # bound by max(rep, 1/rep) when a repetition penalty is active (a penalised negative score is
-    # scaled by rep, its error with it: csrc/runtime.hip issue_decode).  Round 5 shipped c = 0.0043,
+    # scaled by rep, its error with it: csrc/runtime_gpt2.hip issue_decode).  Round 5 shipped c = 0.0043,
     # which counted 2^-8 for BOTH roundings; tests/test_gpu_lm_screen.py builds a near-tie that the
     # old constant gets wrong and this one does not.
     SCREEN_C = 0.0082
