@@ -66,5 +66,11 @@ for _h in (
                "HipMXFP8Linear", "vcap_gemm_mx"),
     PluginHook("vit_layernorm_fp8", "timm LayerNorm feeding an MXFP8 GEMM (BASELINE configs[4])",
                "HipMXFP8LayerNorm", "vcap_layernorm_mx"),
+    PluginHook("l2_normalize", "src/models/vit_text_align.py:54-65 F.normalize (scripts/query_video.py:20-21 l2norm)",
+               "HipL2Normalize", "vcap_l2_normalize"),
+    PluginHook("flat_ip_add", "scripts/build_index.py:40-42 faiss.normalize_L2 + IndexFlatIP.add", "HipFlatIPAdd",
+               "vcap_ip_index_convert"),
+    PluginHook("flat_ip_search", "scripts/query_video.py:127 faiss.IndexFlatIP.search", "HipFlatIPSearch",
+               "vcap_ip_search"),
 ):
     register_plugin_hook(_h)

@@ -27,6 +27,12 @@
  *                           GPT2LMHeadModel.generate greedy with RepetitionPenalty / NoRepeatNGram /
  *                           MinNewTokens, and the raw greedy loop of
  *                           core/scripts/benchmark_baseline.py:160-240 (processors disabled)
+ *   vcap_l2_normalize       F.normalize of ViTTextAlignModel.encode_video (src/models/vit_text_align.py:54-65)
+ *                           and ViTFrameEncoder l2norm (src/models/video_encoder.py:318-319); the l2norm
+ *                           helper of scripts/query_video.py:20-21
+ *   vcap_ip_index_convert / vcap_ip_search
+ *                           faiss.normalize_L2 + IndexFlatIP.add (scripts/build_index.py:40-42) and
+ *                           index.search (scripts/query_video.py:61-75, 127)
  */
 #ifndef VCAP_H_
 #define VCAP_H_
@@ -373,6 +379,58 @@ size_t vcap_gpt2_score_workspace_bytes(const vcap_gpt2_desc* d, int B, int S);
 int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
                     const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
                     size_t ws_bytes, void* stream);
+
+/* ---- video retrieval (added within ABI v16: new symbols only, no struct changes): the inference half of
+ *      the reference's second product - embed a clip, search a flat inner-product index of clip
+ *      embeddings.  Reference interfaces: ViTTextAlignModel.encode_video
+ *      (src/models/vit_text_align.py:54-65) = ViTFrameEncoder(pool="cls", l2norm=True)
+ *      (src/models/video_encoder.py:318-319), i.e. vcap_vit_encode's enc_out followed by
+ *      vcap_l2_normalize; faiss.normalize_L2 + faiss.IndexFlatIP.add (scripts/build_index.py:40-42);
+ *      the l2norm helper, index.search and the printed neighbours of scripts/query_video.py:20-21,
+ *      61-75, 127.  All pointers are device memory; nothing allocates or synchronises; no graph is
+ *      captured, and every call is safe inside a caller's capture.
+ *
+ *      vcap_l2_normalize: rows of f32 [rows, dim] (row strides ldx / ldy, y == x allowed).
+ *        eps_mode 0: y = x / max(||x||, eps)   F.normalize (eps 1e-12); a zero row stays zero, as under
+ *                                              faiss.normalize_L2
+ *        eps_mode 1: y = x / (||x|| + eps)     query_video.py / eval_retrieval.py l2norm (eps 1e-8)
+ *        The sum of squares is an f32 fma chain per lane (elements l, l + 64, ...) and a fixed tree over
+ *        the 64 lanes: a row's result does not depend on `rows`.
+ *      vcap_ip_index_convert: f32 rows [rows, dim] (row stride ldx) -> contiguous index storage
+ *        [rows, dim]: VCAP_DT_F32 a copy, VCAP_DT_BF16 round-to-nearest-even with NaN -> 0x7FC0,
+ *        bit-identical to torch.Tensor.to(torch.bfloat16).  dim % 4 == 0, ldx % 4 == 0, 16-byte aligned
+ *        pointers (VCAP_E_UNSUPPORTED otherwise).
+ *      vcap_ip_search: exact top-k by inner product.  db [n, dim] contiguous, VCAP_DT_F32 or
+ *        VCAP_DT_BF16 (widened to f32, exact); queries [nq, dim] f32; out_scores [nq, k] f32 and out_ids
+ *        [nq, k] int64; max_blocks as vcap_gen_params.max_blocks (0: whole chip).
+ *        Limits (VCAP_E_UNSUPPORTED before any launch): dim % 64 == 0 and 64 <= dim <= 1024;
+ *        1 <= k <= 128; 1 <= nq <= 64 and nq * dim <= 16384; 0 <= n < 2^31 rows (n * dim may pass 2^31:
+ *        offsets are 64-bit); db and queries 16-byte aligned.  Null pointers, negative sizes and other
+ *        dtypes: VCAP_E_ARG.
+ *        Contract: the f32 score of row i against query q is one fixed-order f32 fma chain over the
+ *        row's elements - a function of (row, query, dim, storage dtype) only, not of i, n, nq, the
+ *        query's slot, the grid, max_blocks or a CU mask.  |score - exact| <= 2 * dim * 2^-24 * ||q|| ||x||.
+ *        Results are ordered by score descending, then id ascending (+0 and -0 compare equal), so the
+ *        output is unique: any two calls, grids or batchings of the same rows give the same bits.
+ *        A row whose score is NaN is never returned.  Where fewer than k rows remain (k > n, NaN
+ *        rows) the tail is id -1 with score -inf (our filler; FAISS's own was not available to compare).
+ *        The database is read once per pass of up to 16 * max(1, min(4, 1024 / dim)) queries (one pass
+ *        for nq <= 16 at every dim, for nq <= 64 up to dim 256); dot products run on the f32-input MFMA.
+ *      vcap_ip_search_workspace_bytes: the caller-owned workspace (0 outside the limits): per scan
+ *        workgroup and query k + 2 * vcap_ip_search_slab_rows() 8-byte candidate slots, for
+ *        min(512, ceil(n / slab rows)) workgroups.
+ *      vcap_ip_search_slab_rows / vcap_ip_search_workgroups: the rows a scan workgroup takes per step
+ *        and the scan grid for n rows under max_blocks on the current device (workgroup w takes slabs
+ *        w, w + grid, ...) - for tests that place rows on slab and workgroup boundaries. ---- */
+int vcap_l2_normalize(const float* x, int64_t ldx, float* y, int64_t ldy, int rows, int dim, float eps, int eps_mode,
+                      void* stream);
+int vcap_ip_index_convert(const float* x, int64_t ldx, int rows, int dim, int storage_dtype, void* dst, void* stream);
+size_t vcap_ip_search_workspace_bytes(int64_t n, int dim, int nq, int k);
+int vcap_ip_search(int storage_dtype, const void* db, int64_t n, int dim, const float* queries, int nq, int k,
+                   float* out_scores, int64_t* out_ids, void* workspace, size_t ws_bytes, int max_blocks,
+                   void* stream);
+int vcap_ip_search_slab_rows(void);
+int vcap_ip_search_workgroups(int64_t n, int max_blocks);
 
 /* ---- live kernel timing for the benchmark's roofline (sites: "vit.qkv", "vit.attention",
  *      "vit.proj", "vit.fc1", "vit.fc2"): events are recorded around each launch of the site on

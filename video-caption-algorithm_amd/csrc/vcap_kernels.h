@@ -228,6 +228,21 @@ hipError_t vcap_frames_preprocess_dispatch(const uint8_t* frames, int n, int in_
                                            const float* mean3, const float* std3, float* out, uint8_t* out_u8,
                                            void* ws, hipStream_t s);
 
+// ---- video retrieval (csrc/retrieval.hip): L2 normalisation, index storage conversion, flat-IP top-k ----
+constexpr int kIpSlabRows = 128;           // database rows a scan workgroup takes per step
+constexpr int kIpMaxK = 128;
+constexpr int kIpMaxWorkgroups = 512;      // scan grid cap (the workspace is sized for it)
+constexpr int kIpMaxQueryFloats = 16384;   // nq * dim of one call; one scan launch holds 16-query tiles of it in LDS
+int vcap_ip_search_cap(int k);                      // keys per (workgroup, query) workspace buffer
+int vcap_ip_search_grid(long n, int max_blocks);    // scan workgroups for n rows
+int vcap_ip_search_pass_tiles(int dim);             // 16-query tiles per scan launch (more queries: more passes)
+hipError_t vcap_ip_search_dispatch(int dt, const void* db, long n, int dim, const float* queries, int nq, int k,
+                                   float* out_scores, long long* out_ids, void* workspace, int max_blocks,
+                                   hipStream_t s);
+hipError_t vcap_l2_normalize_dispatch(const float* x, long ldx, float* y, long ldy, int rows, int dim, float eps,
+                                      int eps_mode, hipStream_t s);
+hipError_t vcap_ip_convert_dispatch(int dt, const float* x, long ldx, long rows, int dim, void* dst, hipStream_t s);
+
 // JPEG frame decode (jpeg.hip): header of one baseline image, workspace of n same-shape images,
 // host entropy decode + device IDCT / upsampling / colour conversion into uint8 [n, H, W, 3].
 struct JpegInfo {

@@ -130,6 +130,12 @@ SIGNATURES = {
     "vcap_gpt2_forward_embeds": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "vcap_gpt2_score_workspace_bytes": (sz, [C.POINTER(GPT2Desc), i32, i32]),
     "vcap_gpt2_score": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "vcap_l2_normalize": (i32, [vp, i64, vp, i64, i32, i32, f32, i32, vp]),
+    "vcap_ip_index_convert": (i32, [vp, i64, i32, i32, i32, vp, vp]),
+    "vcap_ip_search_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "vcap_ip_search": (i32, [i32, vp, i64, i32, vp, i32, i32, vp, vp, vp, sz, i32, vp]),
+    "vcap_ip_search_slab_rows": (i32, []),
+    "vcap_ip_search_workgroups": (i32, [i64, i32]),
     "vcap_probe_enable": (i32, [C.c_char_p, i32]),
     "vcap_probe_read": (i32, [C.c_char_p, fp, C.POINTER(C.c_int)]),
     "vcap_probe_read_launches": (i32, [C.c_char_p, fp, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]),
