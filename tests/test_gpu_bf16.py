@@ -333,3 +333,22 @@ def test_decode_attention(device, prec, S_new, past, paged):
     ref = _decode_attn_ref(q, kc, vc, pt, maxp, H, S_new, past)
     tol = 1e-2 if prec == "bf16" else 1e-5
     torch.testing.assert_close(out.float(), ref, rtol=tol, atol=tol)
+
+
+@pytest.mark.parametrize("S_new,past", [(1, 0), (1, 28), (1, 63), (5, 59)])
+def test_decode_attention_kernels_agree(device, S_new, past):
+    """The two decode attention kernel templates compute the same bits: bf16 with an identity page table
+    (the general kernel) against the NULL table (the <= 64 kernel) on the same pools."""
+    seqs, H = 3, 2
+    maxp = (past + S_new + 15) // 16 + 1
+    M = seqs * S_new
+    q = _rand((M, H * 64), 50).to(torch.bfloat16)
+    kc = _rand((seqs * maxp, H, 16, 64), 51).to(torch.bfloat16)
+    vc = _rand((seqs * maxp, H, 16, 64), 52).to(torch.bfloat16)
+    outs = []
+    for pt in (torch.arange(seqs * maxp, dtype=torch.int32, device=device), None):
+        out = torch.zeros(M, H * 64, dtype=torch.bfloat16, device=device)
+        N.check(N.lib().vcap_decode_attention(N.DT_BF16, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), N.ptr(pt), maxp,
+                                              out.data_ptr(), M, H, S_new, past, _stream()), "decode attention")
+        outs.append(out.view(torch.int16))
+    assert torch.equal(outs[0], outs[1])

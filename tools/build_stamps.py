@@ -77,18 +77,6 @@ def patch_decode(s: str) -> str:
                         "  if (threadIdx.x == 0) vcap_stamp_rec((unsigned long long)((NSL << 12) | (EPI << 8) | (PRO << 4) | NTB) | ((unsigned long long)MT << 20) | ((unsigned long long)(hsel >= 0) << 24), t0, t1, tw, t2, t3, VCAP_RT());\n}", 1)
     assert body.count("VCAP_RT()") == 6, body.count("VCAP_RT()")
     s = s[:k0] + body + s[k1:]
-    # decode attention (c64, both element types): entry | every load landed | output stored (issued)
-    a0 = s.index("void vcap_decode_attention_c64_kernel(")
-    a1 = s.index("hipError_t vcap_decode_attention_dispatch(", a0)
-    att = s[a0:a1]
-    att = att.replace("  __shared__ float s_p[64];\n", "  __shared__ float s_p[64];\n  const unsigned long long t0 = VCAP_RT();\n", 1)
-    att = att.replace("  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n",
-                      "  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);\n"
-                      "  asm volatile(\"\" :: \"v\"(L.vv[7][C64Loads<T>::NV - 1].x));\n"
-                      "  const unsigned long long t1 = VCAP_RT();\n", 1)
-    att = att[:att.rindex("}")] + "  if (threadIdx.x == 0) vcap_stamp_rec(0xA000ull, t0, t1, t1, t1, t1, VCAP_RT());\n}\n\n"
-    assert att.count("VCAP_RT()") == 3, att.count("VCAP_RT()")
-    s = s[:a0] + att + s[a1:]
     # lm_head stream kernel (greedy / screen): entry | ln_f tile in LDS (+ flags zeroed) | first column
     # group done | second group done | last group done | argmax partials written  (tag 0xC000).  The
     # stamps sit in the walker it shares with the beam search's LSE kernel; only the greedy sink records.
@@ -110,6 +98,23 @@ def patch_decode(s: str) -> str:
     assert lm.count("VCAP_RT()") == 6, lm.count("VCAP_RT()")
     s = s[:l0] + lm + s[l1:]
     return s
+
+
+def patch_decode_attention(s: str) -> str:
+    # the <= 64 decode attention kernel (every key source and element type): entry | every load landed |
+    # output stored (issued).  Its own buffer and reader (vcap_diag_stamps_dattn): another translation unit.
+    s = s.replace('#include "vcap_kernels.h"\n', '#include "vcap_kernels.h"\n' + header("_dattn"), 1)
+    a0 = s.index("void vcap_decode_attention_c64_kernel(")
+    a1 = s.rindex("// ----", a0, s.index("// Launches.", a0))
+    att = s[a0:a1]
+    att = att.replace("  __shared__ float s_p[WAVES][64];\n",
+                      "  __shared__ float s_p[WAVES][64];\n  const unsigned long long t0 = VCAP_RT();\n", 1)
+    issue = "  c64_issue<T>(L, q, kc, vc, keys, seq, m, h, H, ctx, s_q[wave], s_a[wave]);\n"
+    att = att.replace(issue, issue + "  asm volatile(\"\" :: \"v\"(L.vv[7][C64Loads<T>::NV - 1].x));\n"
+                      "  const unsigned long long t1 = VCAP_RT();\n", 1)
+    att = att[:att.rindex("}")] + "  if (threadIdx.x == 0) vcap_stamp_rec_dattn(0xA000ull, t0, t1, t1, t1, t1, VCAP_RT());\n}\n\n"
+    assert att.count("VCAP_RT()") == 3, att.count("VCAP_RT()")
+    return s[:a0] + att + s[a1:]
 
 
 def patch_attention(s: str) -> str:
@@ -137,6 +142,8 @@ def main():
         shutil.copy(f, src / f.name)
     p = src / "decode.hip"
     p.write_text(patch_decode(p.read_text()))
+    p = src / "decode_attention.hip"
+    p.write_text(patch_decode_attention(p.read_text()))
     p = src / "vit_attention.hip"
     p.write_text(patch_attention(p.read_text()))
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-Wno-unused-result",

@@ -48,8 +48,10 @@ def main():
     prec = os.environ.get("PREC", "bf16")
     dec = HipGPT2Decoder(weights.synthetic_gpt2(1, ga), ga, prec, dev)
     lib = N.lib()
-    lib.vcap_diag_stamps.restype = C.c_int
-    lib.vcap_diag_stamps.argtypes = [C.c_void_p, C.c_int]
+    readers = (lib.vcap_diag_stamps, lib.vcap_diag_stamps_dattn)   # decode.hip's and decode_attention.hip's buffers
+    for fn in readers:
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int]
     B = int(os.environ.get("B", "8"))
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -59,12 +61,16 @@ def main():
         for _ in range(3):
             dec.generate_ids(pre, [ga.bos_token_id], cfg)
         torch.cuda.synchronize()
-        lib.vcap_diag_stamps(None, 0)
+        for fn in readers:
+            fn(None, 0)
         dec.generate_ids(pre, [ga.bos_token_id], cfg)
         torch.cuda.synchronize()
-    buf = np.zeros((1 << 18, 8), dtype=np.uint64)
-    n = lib.vcap_diag_stamps(buf.ctypes.data, buf.shape[0])
-    rec = buf[:n].astype(np.int64)
+    parts = []
+    for fn in readers:
+        buf = np.zeros((1 << 18, 8), dtype=np.uint64)
+        parts.append(buf[:fn(buf.ctypes.data, buf.shape[0])])
+    rec = np.concatenate(parts).astype(np.int64)
+    n = len(rec)
     rec = rec[np.argsort(rec[:, 2], kind="stable")]
     # split into launches: consecutive records (by entry time) with the same tag and grid
     launches, cur = [], []

@@ -271,133 +271,6 @@ constexpr bool gemv_stream_a() {
 }
 
 // ------------------------------------------------------------------------------------------------
-// One (row m, head h) item of causal decode attention over <= 64 cached positions in the
-// contiguous page layout the runtime allocates (page of position j of sequence `seq` =
-// seq * maxp + j / 16: page ids are computed, not loaded), on ONE wave: scores with lane = key,
-// P.V with lane = (key group kg of 8, 8 consecutive dims d8), partial sums reduced over the 8 key
-// groups by DPP + permlane swaps.  c64_issue issues every load of the item at once (q, the lane's
-// K row, its 8 V rows: one memory round trip); c64_finish is the arithmetic, the ONE operation
-// order of vcap_decode_attention_c64_kernel: the score sums dims 0..63 in order, and the P.V sums run
-// over the same key groups and reduction as vcap_decode_attention_kernel<T>.
-template <typename T>
-struct C64Loads {
-  static constexpr int E8 = Frag<T>::kElems, NK = 64 / E8, NV = 8 / E8;  // bf16: 8, 8, 1; f32: 4, 16, 2
-  u32x4 q;          // E8 of the head's 64 query dims: chunk (lane & (NK - 1))
-  u32x4 kv[NK];     // K row of key min(lane, ctx - 1)
-  u32x4 vv[8][NV];  // V rows of keys it * 8 + kg (clamped), dims [d8, d8 + 8)
-};
-
-// the E8 elements of a 16-byte chunk as floats, in memory order
-template <typename T>
-VCAP_DEV void chunk_to_f(const u32x4& v, float (&f)[Frag<T>::kElems]) {
-  if constexpr (sizeof(T) == 2) {
-    const unsigned w4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[2 * e] = bf2f((bf16_t)(w4[e] & 0xffff));
-      f[2 * e + 1] = bf2f((bf16_t)(w4[e] >> 16));
-    }
-  } else {
-    const f32x4 v4 = __builtin_bit_cast(f32x4, v);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f[e] = v4[e];
-  }
-}
-
-// 8 consecutive output dims o[] * inv -> orow (16-byte aligned)
-template <typename T>
-VCAP_DEV void store_out8(T* orow, const float (&o)[8], float inv) {
-  if constexpr (sizeof(T) == 2) {
-    *reinterpret_cast<u32x4*>(orow) =
-        (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv),
-                pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
-  } else {
-    *reinterpret_cast<f32x4*>(orow) = (f32x4){o[0], o[1], o[2], o[3]} * inv;
-    *reinterpret_cast<f32x4*>(orow + 4) = (f32x4){o[4], o[5], o[6], o[7]} * inv;
-  }
-}
-
-template <typename T>
-VCAP_DEV void c64_issue(C64Loads<T>& L, const T* q, const T* kc, const T* vc, int maxp, int m, int h, int H, int seq,
-                        int ctx) {
-  constexpr int E8 = C64Loads<T>::E8, NK = C64Loads<T>::NK, NV = C64Loads<T>::NV;
-  const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
-  auto row_of = [&](int j) { return (((long)(seq * maxp + (j >> 4)) * H + h) * 16 + (j & 15)) * 64; };
-  auto ld = [](const T* base, long elem) { return *reinterpret_cast<const u32x4*>(base + elem); };
-  L.q = ld(q, (long)m * H * 64 + h * 64 + (lane & (NK - 1)) * E8);
-  const long kr = row_of(min(lane, ctx - 1));
-#pragma unroll
-  for (int c = 0; c < NK; ++c) L.kv[c] = ld(kc, kr + c * E8);
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const long vr = row_of(min(it * 8 + kg, ctx - 1)) + d8;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) L.vv[it][v] = ld(vc, vr + v * E8);
-  }
-}
-
-// Optional per-sequence key mask of the attention kernels (teacher-forced scoring: vcap_gpt2_score).
-// A hidden key's score is -inf before the softmax.  KeyMask<false> is empty and hides nothing, so the
-// unmasked instantiations are today's kernels.  Key 0 of every sequence must be visible (a row with no
-// visible key has no softmax).
-template <bool MASKED>
-struct KeyMask {
-  VCAP_DEV bool hidden(int, int) const { return false; }
-};
-template <>
-struct KeyMask<true> {
-  const uint8_t* m;  // [seqs][ld]: 0 = key hidden from every query of its sequence
-  int ld;
-  VCAP_DEV bool hidden(int seq, int j) const { return m[(long)seq * ld + j] == 0; }
-};
-
-// s_q / s_p: this wave's 64 floats each of LDS (s_q 16-byte aligned); orow = out + m * E + h * 64;
-// vis: key `lane` is not hidden by a key mask
-template <typename T>
-VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, T* orow, bool vis = true) {
-  constexpr int E8 = C64Loads<T>::E8, NK = C64Loads<T>::NK, NV = C64Loads<T>::NV;
-  const int lane = threadIdx.x & 63, kg = lane >> 3, d8 = (lane & 7) * 8;
-  float f[E8];
-  if (lane < NK) {
-    chunk_to_f<T>(L.q, f);
-#pragma unroll
-    for (int e = 0; e < E8; ++e) s_q[lane * E8 + e] = f[e];
-  }
-  __builtin_amdgcn_wave_barrier();
-  float sc = 0.f;
-#pragma unroll
-  for (int c = 0; c < NK; ++c) {
-    chunk_to_f<T>(L.kv[c], f);
-#pragma unroll
-    for (int e = 0; e < E8; ++e) sc += s_q[c * E8 + e] * f[e];
-  }
-  sc *= 0.125f;
-  const bool live = lane < ctx && vis;
-  const float mx = wave_max(live ? sc : -INFINITY);
-  const float p = live ? __expf(sc - mx) : 0.f;
-  const float sum = wave_sum(p);
-  s_p[lane] = p;
-  __builtin_amdgcn_wave_barrier();
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const int jj = it * 8 + kg;
-    const float pj = jj < ctx ? s_p[jj] : 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      chunk_to_f<T>(L.vv[it][v], f);
-#pragma unroll
-      for (int e = 0; e < E8; ++e) o[v * E8 + e] += pj * f[e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = rows_sum(o[e] + dpp_f<0x128>(o[e]));
-  if (kg == 0) store_out8<T>(orow + d8, o, 1.0f / sum);
-}
-
-// ------------------------------------------------------------------------------------------------
 // K split of the residual GEMVs (the mlp c_proj).  The host's rows_split_plan (beside the dispatcher)
 // is the one place that decides whether a launch splits and into what; a kernel splits when the
 // launch carries a.sk_part AND its instantiation can (rows_can_split: the compile-time guard, so an
@@ -878,88 +751,6 @@ __global__ __launch_bounds__(256) void vcap_rows_gemm_lds_kernel(RowsGemmArgs a)
   if constexpr (EPI == EPI_LOGITS) toks.mark(a, m0, n0, NTB * 16, &s_rep[0][0], &s_ban[0][0], NTB * 16);
   __syncthreads();
   rows_epilogue<T, MT, NTB, EPI>(a, m0, red, pre_bias, pre_res, lg, s_rep, s_ban, n0);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Causal attention of S_new query rows per sequence over the paged cache (positions 0..past+i).
-// One wave per (row, head).  The sequence's page ids are read once (lane p holds page p) and
-// broadcast with ds_bpermute, so no K/V load waits on a dependent page-table load.
-// Scores: lane j <-> key j (+64 ...), full 64-dim dot.  P.V: lane = (key group kg of 8, 8
-// consecutive dims d8), partial sums reduced over the 8 key groups by DPP + permlane swaps.
-template <typename T, bool MASKED = false>
-__global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __restrict__ q, const T* __restrict__ kc,
-                                                                    const T* __restrict__ vc,
-                                                                    const int* __restrict__ page_table, int maxp,
-                                                                    T* __restrict__ out, int M, int H, int S_new,
-                                                                    int past, KeyMask<MASKED> km) {
-  constexpr int E8 = Frag<T>::kElems;  // elements per 16-byte chunk
-  __shared__ float s_q[4][64];
-  __shared__ float s_p[4][1024];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int item = blockIdx.x * 4 + wave;
-  if (item >= M * H) return;
-  const int m = item / H, h = item - m * H;
-  const int E = H * 64;
-  const int seq = m / S_new, qpos = past + (m - seq * S_new);
-  const int ctx = qpos + 1;
-  const int my_page = page_table[seq * maxp + min(lane, maxp - 1)];
-  s_q[wave][lane] = Num<T>::to_f(q[(long)m * E + h * 64 + lane]);
-  __builtin_amdgcn_wave_barrier();
-  float mx = -INFINITY;
-  for (int j0 = 0; j0 < ctx; j0 += 64) {
-    const int j = min(j0 + lane, ctx - 1);
-    const int page = __shfl(my_page, j >> 4);
-    const T* krow = kc + (((long)page * H + h) * 16 + (j & 15)) * 64;
-    u32x4 kv[64 / E8];
-#pragma unroll
-    for (int c = 0; c < 64 / E8; ++c) kv[c] = *reinterpret_cast<const u32x4*>(krow + c * E8);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 64 / E8; ++c) {
-      const T* ke = reinterpret_cast<const T*>(&kv[c]);
-#pragma unroll
-      for (int e = 0; e < E8; ++e) s += s_q[wave][c * E8 + e] * Num<T>::to_f(ke[e]);
-    }
-    s *= 0.125f;
-    if (j0 + lane < ctx) {
-      if constexpr (MASKED)
-        if (km.hidden(seq, j0 + lane)) s = -INFINITY;
-      s_p[wave][j0 + lane] = s;
-      mx = fmaxf(mx, s);
-    }
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < ctx; j += 64) {
-    const float p = __expf(s_p[wave][j] - mx);
-    s_p[wave][j] = p;
-    sum += p;
-  }
-  sum = wave_sum(sum);
-  __builtin_amdgcn_wave_barrier();
-  const int kg = lane >> 3, d8 = (lane & 7) * 8;
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll 4
-  for (int j0 = 0; j0 < ctx; j0 += 8) {
-    const int jj = j0 + kg;
-    const int j = min(jj, ctx - 1);
-    const int page = __shfl(my_page, j >> 4);
-    const T* vrow = vc + (((long)page * H + h) * 16 + (j & 15)) * 64 + d8;
-    const float p = jj < ctx ? s_p[wave][j] : 0.f;
-#pragma unroll
-    for (int v = 0; v < 8 / E8; ++v) {
-      float f[E8];
-      chunk_to_f<T>(*reinterpret_cast<const u32x4*>(vrow + v * E8), f);
-#pragma unroll
-      for (int e = 0; e < E8; ++e) o[v * E8 + e] += p * f[e];
-    }
-  }
-  // reduce over the 8 key groups: lane ^ 8 (row_ror:8 inside a 16-lane row), then ^16, ^32
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = rows_sum(o[e] + dpp_f<0x128>(o[e]));
-  if (kg == 0) store_out8<T>(out + (long)m * E + h * 64 + d8, o, 1.0f / sum);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1739,67 +1530,6 @@ hipError_t vcap_rows_pack_dispatch(int dt, const void* w, long ldw, int N, int K
 size_t vcap_rows_packed_size(int dt, int N, int K) {
   const int ks = dt == VCAP_DT_BF16 ? 32 : 16;
   return (size_t)((N + 15) / 16) * (size_t)(K / ks) * 1024;
-}
-
-// Fast path for contexts of at most 64 positions with the contiguous page layout the
-// runtime allocates (page of position j of sequence `seq` = seq * maxp + j / 16, i.e. the identity
-// page table): page ids are computed, not loaded, and q, the lane's K row and all of its V rows
-// are issued together, so the wave pays ONE memory round trip instead of three
-// (page table -> K -> V).  Arithmetic identical to vcap_decode_attention_kernel.
-template <typename T, bool MASKED = false>
-__global__ __launch_bounds__(64) void vcap_decode_attention_c64_kernel(const T* __restrict__ q, const T* __restrict__ kc,
-                                                                       const T* __restrict__ vc, int maxp,
-                                                                       T* __restrict__ out, int M, int H, int S_new,
-                                                                       int past, KeyMask<MASKED> km) {
-  __shared__ __attribute__((aligned(16))) float s_q[64];
-  __shared__ float s_p[64];
-  const int item = blockIdx.x;  // one 64-thread workgroup per (row, head)
-  if (item >= M * H) return;
-  const int m = item / H, h = item - m * H;
-  const int seq = m / S_new, qpos = past + (m - seq * S_new);
-  const int ctx = qpos + 1;  // <= 64 (dispatcher)
-  C64Loads<T> L;
-  c64_issue<T>(L, q, kc, vc, maxp, m, h, H, seq, ctx);
-  bool vis = true;
-  if constexpr (MASKED) vis = !km.hidden(seq, min((int)threadIdx.x, ctx - 1));
-  c64_finish<T>(L, s_q, s_p, ctx, out + (long)m * H * 64 + h * 64, vis);
-}
-
-template <bool MASKED>
-static hipError_t launch_decode_attention(int dt, const void* q, const void* kc, const void* vc, const int* pt, int maxp,
-                                          void* out, int M, int H, int S_new, int past, hipStream_t s,
-                                          KeyMask<MASKED> km) {
-  const dim3 grid((M * H + 3) / 4), block(256);
-  if (!pt && past + S_new <= 64 && (dt == VCAP_DT_BF16 || dt == VCAP_DT_F32)) {
-    // one 64-thread workgroup per (row, head): the ~100-200 items of a decode step spread over as
-    // many CUs (each item's q / K / V round trip on a CU of its own) instead of 4 per CU
-    if (dt == VCAP_DT_BF16)
-      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<bf16_t, MASKED>), dim3(M * H), dim3(64), 0, s,
-                         (const bf16_t*)q, (const bf16_t*)kc, (const bf16_t*)vc, maxp, (bf16_t*)out, M, H, S_new, past,
-                         km);
-    else
-      hipLaunchKernelGGL((vcap_decode_attention_c64_kernel<float, MASKED>), dim3(M * H), dim3(64), 0, s,
-                         (const float*)q, (const float*)kc, (const float*)vc, maxp, (float*)out, M, H, S_new, past, km);
-    return hipGetLastError();
-  }
-  if (!pt) return hipErrorInvalidValue;  // the general kernels read the page table
-  if (dt == VCAP_DT_BF16)
-    hipLaunchKernelGGL((vcap_decode_attention_kernel<bf16_t, MASKED>), grid, block, 0, s, (const bf16_t*)q,
-                       (const bf16_t*)kc, (const bf16_t*)vc, pt, maxp, (bf16_t*)out, M, H, S_new, past, km);
-  else
-    hipLaunchKernelGGL((vcap_decode_attention_kernel<float, MASKED>), grid, block, 0, s, (const float*)q,
-                       (const float*)kc, (const float*)vc, pt, maxp, (float*)out, M, H, S_new, past, km);
-  return hipGetLastError();
-}
-
-// kmask [seqs][mask_ld] (optional): the masked instantiations of the same two kernels
-hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
-                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s,
-                                          const uint8_t* kmask, int mask_ld) {
-  if (past + S_new > 1024 || maxp > 64) return hipErrorInvalidValue;
-  if (!kmask) return launch_decode_attention(dt, q, kc, vc, pt, maxp, out, M, H, S_new, past, s, KeyMask<false>{});
-  if (mask_ld < past + S_new) return hipErrorInvalidValue;
-  return launch_decode_attention(dt, q, kc, vc, pt, maxp, out, M, H, S_new, past, s, KeyMask<true>{kmask, mask_ld});
 }
 
 hipError_t vcap_prefill_embed_dispatch(int dt, const float* prefix, int P, const int* ids, int nids, const void* wte,

@@ -151,15 +151,11 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
     VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_LN, EPI_QKV, a, nullptr, s), "c_attn");
     // 2) causal attention over the paged cache
     // pages are allocated contiguously per sequence (vcap_decode_init: identity table), so the
-    // short-context kernels (bf16 and f32) compute page ids instead of loading them (nullptr table)
-    const int* pt_arg = past + S_new <= 64 ? nullptr : w.pt;
-    if (x.anc)
-      VCAP_TRY(vcap_decode_attention_anc_dispatch(dt, w.q, a.kc, a.vc, x.anc, x.anc_ld, w.maxp, w.attn, M, H, past, s),
-               "decode_attention_anc");
-    else
-      VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, pt_arg, w.maxp, w.attn, M, H, S_new, past, s,
-                                              x.kmask, x.mask_ld),
-               "decode_attention");
+    // short-context kernels (bf16 and f32) compute page ids instead of loading them (nullptr table);
+    // beam search reads through its ancestry table instead
+    const DecodeKeys keys{x.anc || past + S_new <= 64 ? nullptr : w.pt, x.anc, x.anc_ld, x.kmask, x.mask_ld};
+    VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, keys, w.maxp, w.attn, M, H, S_new, past, s),
+             "decode_attention");
     // 3) attn c_proj + residual
     RowsGemmArgs b{};
     b.M = M; b.x = w.attn; b.ldx = E; b.w = ly.aproj_w; b.bias = ly.aproj_b; b.N = E; b.K = E;
@@ -494,7 +490,9 @@ int vcap_decode_attention(int dtype, const void* q, const void* k_pool, const vo
   if (past + S_new > 16 * maxp) return fail(VCAP_E_ARG, "vcap_decode_attention: context exceeds the page table");
   if (!page_table && (dtype != VCAP_DT_BF16 || past + S_new > 64))
     return fail(VCAP_E_UNSUPPORTED, "vcap_decode_attention: a NULL page table needs bf16 and context <= 64");
-  VCAP_TRY(vcap_decode_attention_dispatch(dtype, q, k_pool, v_pool, page_table, maxp, out, M, heads, S_new, past,
+  DecodeKeys keys;
+  keys.page_table = page_table;
+  VCAP_TRY(vcap_decode_attention_dispatch(dtype, q, k_pool, v_pool, keys, maxp, out, M, heads, S_new, past,
                                           (hipStream_t)stream),
            "vcap_decode_attention");
   return 0;

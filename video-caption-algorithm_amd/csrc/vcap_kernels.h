@@ -150,11 +150,23 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
 hipError_t vcap_rows_pack_dispatch(int dt, const void* w, long ldw, int N, int K, void* packed, hipStream_t s);
 size_t vcap_rows_packed_size(int dt, int N, int K);
 int vcap_logit_blocks(int V, int M);
-// kmask (optional) [seqs][mask_ld] bytes: key j of a sequence with kmask[seq][j] == 0 is hidden from every
-// query of that sequence (score -inf before the softmax); key 0 must be visible
-hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* pt,
-                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s,
-                                          const uint8_t* kmask = nullptr, int mask_ld = 0);
+// ---- decode attention (csrc/decode_attention.hip): S_new query rows per sequence, keys 0..past+i ----
+// Where the keys of row m live, and which of them it may see.
+struct DecodeKeys {
+  // [seqs][maxp] page ids (maxp <= 64), or nullptr: the contiguous layout, page of position j of sequence
+  // seq = seq * maxp + j / 16, which only contexts <= 64 take without a table
+  const int* page_table = nullptr;
+  // [M][anc_ld] (beam search; S_new == 1, no mask) or nullptr: key j of row m is position j of physical row
+  // anc[m * anc_ld + j] of the contiguous layout; page_table is not read
+  const int* anc = nullptr;
+  int anc_ld = 0;
+  // [seqs][mask_ld] bytes or nullptr: key j of a sequence with kmask[seq][j] == 0 is hidden from every query
+  // of that sequence (score -inf before the softmax); key 0 must be visible
+  const uint8_t* kmask = nullptr;
+  int mask_ld = 0;
+};
+hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const DecodeKeys& keys,
+                                          int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s);
 // ---- teacher-forced scoring (csrc/score.hip): lm_head + cross-entropy over every row ----
 struct ScoreLmArgs {
   const void* xn;       // [M][E] ln_f rows in the decoder dtype
@@ -215,11 +227,6 @@ hipError_t vcap_beam_select_dispatch(const BeamState& st, int B, int nb, int L, 
 hipError_t vcap_beam_output_dispatch(const BeamState& st, int B, int nb, int L, int* out_ids, int* out_len,
                                      hipStream_t s);
 int vcap_beam_chunks(int V);
-// causal decode attention (one query row per sequence) whose key j of row m lives in physical
-// row anc[m * anc_ld + j] of the contiguous-page pools (beam search: no KV copies on reorder)
-hipError_t vcap_decode_attention_anc_dispatch(int dt, const void* q, const void* kc, const void* vc, const int* anc,
-                                              int anc_ld, int maxp, void* out, int M, int H, int past,
-                                              hipStream_t s);
 
 hipError_t vcap_kv_gather_dispatch(int dt, const void* src_pool, void* dst_pool, const int* src_rows, int rows, int maxp,
                                    int H, int len, long layer_elems, int L, hipStream_t s);
