@@ -280,7 +280,16 @@ int vcap_gpt2_generate(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const
  *      warped_out (optional, [max_new][B][vocab] f32): the warped scores each draw used (-inf where
  *      removed), i.e. HF's output_scores; force_ids (optional, [B][max_new]): emit these tokens
  *      instead of drawing (tests replay a recorded history).  Parity with the reference is
- *      distributional: the RNG streams differ. ---- */
+ *      distributional: the RNG streams differ.
+ *      The draw: u = (word 0 of Philox4x32-10(counter (step, row, 0, 0), key (seed low, seed high))
+ *      >> 8) / 2^24; the kept tokens are walked ascending by score, ties by vocabulary index, and the
+ *      token is the first whose cumulative exp(s - max) exceeds u * total.  A row without a finite
+ *      score emits EOS without a draw.
+ *      One departure from HF: top-k keeps every score tied at the k-th value, and so does HF, but
+ *      the kernel holds at most 256 survivors.  A row with more (over 256 - (k - 1) scores tied at
+ *      the threshold) keeps every score strictly above the threshold and then the tied tokens of
+ *      lowest vocabulary index until 256 are kept; top-p and the draw run over those 256.  The
+ *      result is deterministic: the same row gives the same support and the same token. ---- */
 typedef struct vcap_sample_params {
   float temperature;  /* > 0 */
   int top_k;          /* HF generation-config default 50; 1..128 */

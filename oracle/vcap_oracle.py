@@ -21,7 +21,9 @@ A plain fp32 restatement (torch CPU tensors used as an array library) of:
     RepetitionPenalty -> NoRepeatNGram -> MinNewTokens(=MinLength) -> argmax,
     EOS padding, stop when all finished (transformers 5.15.0 in this image,
     generation/utils.py:1174-1237 and logits_process.py; SURVEY.md §8c);
-  * the benchmark's raw greedy loop (core/scripts/benchmark_baseline.py:160-240).
+  * the benchmark's raw greedy loop (core/scripts/benchmark_baseline.py:160-240);
+  * HF `generate`'s sampling warpers (Temperature -> TopK -> TopP, logits_process.py) and the
+    device's documented draw (Philox4x32-10 uniform, inverse CDF over the kept tokens).
 
 Parity pin: tests/golden/make_goldens.py runs the reference's own code
 (ViTFrameEncoder, InferenceEngine._generate_once, GPT2TextDecoder.generate)
@@ -410,6 +412,83 @@ def caption_ids(sd, vit_arch, gpt_arch, video: Tensor, prompt_ids: Sequence[int]
     gen_kw.pop("num_beams", None)
     ids, _ = generate_greedy(sd, gpt_arch, x, **gen_kw)
     return ids
+
+
+# ----------------------------------------------------------------------------- sampling (HF _sample)
+# HF generate with do_sample: the processors above, then TemperatureLogitsWarper -> TopKLogitsWarper ->
+# TopPLogitsWarper (transformers generation/logits_process.py), then one multinomial draw per row.
+# The warpers are restated here (tests/test_cpu_sampling_cases.py pins them bit for bit to HF's own
+# classes); the draw is the device's documented one (csrc/sample.hip): a Philox4x32-10 uniform and an
+# inverse CDF over the kept tokens in ascending order.
+
+def warp_scores(scores: Tensor, temperature: float, top_k: int, top_p: float) -> Tensor:
+    """scores [B, V] f32 (processed) -> warped scores [B, V] f32, -inf where removed.  The top-p warper
+    is left out at top_p == 1.0, as HF's generate leaves it out; min_tokens_to_keep is 1.
+    Where the top-p cut falls inside a group of equal scores, which of them go is the choice of
+    torch.sort (HF's call, not a stable sort); the device drops those of lowest vocabulary index."""
+    s = scores / temperature
+    k = min(int(top_k), s.shape[-1])
+    s = s.masked_fill(s < torch.topk(s, k)[0][..., -1, None], -float("inf"))   # ties at the k-th value stay
+    if top_p < 1.0:
+        srt, idx = torch.sort(s, descending=False)
+        remove = srt.softmax(dim=-1).cumsum(dim=-1) <= (1 - top_p)
+        remove[..., -1:] = False                                    # the largest is always kept
+        s = s.masked_fill(remove.scatter(-1, idx, remove), -float("inf"))
+    return s
+
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter4: Sequence[int], key2: Sequence[int]) -> Tuple[int, int, int, int]:
+    """Philox4x32 with 10 rounds (Salmon et al., Random123) on 32-bit words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter4)
+    k0, k1 = (int(k) & _M32 for k in key2)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed: int, row: int, step: int) -> float:
+    """The uniform of (seed, row, step): counter (step, row, 0, 0), key (seed low word, seed high
+    word), the top 24 bits of the first output word -> u in [0, 1), a multiple of 2^-24."""
+    w0 = philox4x32_10((step, row, 0, 0), (seed & _M32, (seed >> 32) & _M32))[0]
+    return (w0 >> 8) / float(1 << 24)
+
+
+def _ascending_mass(row: Tensor) -> Tuple[Tensor, Tensor]:
+    """The finite entries of a row in ascending order (ties by vocabulary index) -> (their indices,
+    cumulative exp(s - max) / total in float64)."""
+    row = row.double()
+    kept = torch.nonzero(torch.isfinite(row)).flatten()
+    vals, order = torch.sort(row[kept], stable=True)
+    cum = torch.exp(vals - vals[-1]).cumsum(0)
+    return kept[order], cum / cum[-1]
+
+
+def draw(warped_row: Tensor, u: float) -> Tuple[int, float]:
+    """Inverse-CDF draw from softmax(warped_row): the kept (finite) tokens are walked ascending by
+    value, ties by vocabulary index, and the token is the first whose cumulative mass exceeds
+    u * total.  -> (token, margin); margin = min_j |u - C_j / total|, how far u is from a different draw."""
+    idx, cdf = _ascending_mass(warped_row)
+    j = min(int(torch.searchsorted(cdf, torch.tensor(u, dtype=torch.float64), right=True)), len(idx) - 1)
+    return int(idx[j]), float((cdf - u).abs().min())
+
+
+def top_p_margin(processed_row: Tensor, temperature: float, top_k: int, top_p: float) -> float:
+    """How far the top-p cut of one processed f32 row is from keeping a different set: the smallest
+    |cumsum_j - (1 - top_p)| of the ascending cumulative softmax (float64) over the top-k survivors.
+    The last cumsum (1.0, the largest token) is left out: that token is kept whatever it compares to,
+    and counting it would put every row of a tiny top_p within top_p of a cut that cannot happen.
+    inf at top_p == 1 (no top-p warper runs) and where one score survives top-k."""
+    if top_p >= 1.0:
+        return float("inf")
+    s = warp_scores(processed_row.float()[None], temperature, top_k, 1.0)[0]
+    _, cdf = _ascending_mass(s)
+    return float((cdf[:-1] - (1.0 - top_p)).abs().min()) if len(cdf) > 1 else float("inf")
 
 
 # ----------------------------------------------------------------------------- MXFP8 (configs[4])

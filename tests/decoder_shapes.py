@@ -39,14 +39,16 @@ LONG_E, LONG_B, LONG_PROMPT = 384, 3, 50   # S0 = 54: the context crosses 64 at 
 _PREFIX_RESEED = {(768, 1): 2, (896, 5): 3, (LONG_E, LONG_B): 1}
 
 
-def arch(E: int) -> GPT2Arch:
-    return GPT2Arch(f"sweep_{E}", E, NLAYER, E // 64, vocab=VOCAB, n_positions=NPOS,
-                    bos_token_id=VOCAB - 1, eos_token_id=VOCAB - 1)
+def arch(E: int, vocab: int = VOCAB) -> GPT2Arch:
+    """`vocab` other than the sweep's 1000: the sampling sweep's models (tests/sampling_cases.py)."""
+    name = f"sweep_{E}" if vocab == VOCAB else f"sweep_{E}_v{vocab}"
+    return GPT2Arch(name, E, NLAYER, E // 64, vocab=vocab, n_positions=NPOS,
+                    bos_token_id=vocab - 1, eos_token_id=vocab - 1)
 
 
 @lru_cache(maxsize=None)
-def state_dict(E: int):
-    return weights.synthetic_gpt2(WEIGHT_SEED, arch(E))
+def state_dict(E: int, vocab: int = VOCAB):
+    return weights.synthetic_gpt2(WEIGHT_SEED, arch(E, vocab))
 
 
 def prefix(E: int, B: int) -> torch.Tensor:
@@ -73,10 +75,10 @@ _MATS = ("attn.c_attn.weight", "attn.c_proj.weight", "mlp.c_fc.weight", "mlp.c_p
 
 
 @lru_cache(maxsize=None)
-def sd64(E: int, rounded: bool = False):
+def sd64(E: int, rounded: bool = False, vocab: int = VOCAB):
     """The state dict as float64 tensors; `rounded`: projection weights and wte on the bf16 grid."""
     out = {}
-    for k, v in state_dict(E).items():
+    for k, v in state_dict(E, vocab).items():
         t = torch.from_numpy(np.ascontiguousarray(v)).double()
         if rounded and (k.endswith(_MATS) or k in (WTE, "decoder.model.lm_head.weight")):
             t = bf16_rne(t)
@@ -113,13 +115,14 @@ def emulated_forward(sd, ar, inputs_embeds, cache, rnd=bf16_rne):
     return h @ sd["decoder.model.lm_head.weight"].t()
 
 
-def teacher_forced(E: int, pre: torch.Tensor, prompt_ids, ids, mode: str = "fp64") -> torch.Tensor:
+def teacher_forced(E: int, pre: torch.Tensor, prompt_ids, ids, mode: str = "fp64",
+                   vocab: int = VOCAB) -> torch.Tensor:
     """Raw logits [B, steps, V] (float64) of every generation step along the given ids [B, steps]:
     one forward over build_inputs(prefix, prompt) followed by wte[ids[:, :-1]] with a fresh cache.
     mode "fp64": oracle.gpt2_forward on the float64 weights; "bf16": emulated_forward on the
     bf16-rounded weights; "ident": emulated_forward with rounding switched off."""
-    ar = arch(E)
-    sd = sd64(E, rounded=(mode == "bf16"))
+    ar = arch(E, vocab)
+    sd = sd64(E, rounded=(mode == "bf16"), vocab=vocab)
     ids = torch.as_tensor(np.asarray(ids), dtype=torch.long)
     x = torch.cat([O.build_inputs(sd, ar, pre.double(), prompt_ids), sd[WTE][ids[:, :-1]]], dim=1)
     s0 = pre.shape[1] + len(prompt_ids)

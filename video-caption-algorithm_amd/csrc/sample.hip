@@ -12,7 +12,10 @@
 //                            Philox4x32-10 stream keyed on (seed, row, step)
 // The 50th largest is found exactly by bisection on an order-preserving 32-bit key (32 block-wide
 // counts), the <= 256 survivors are ranked in LDS, and lane 0 of wave 0 runs top-p's cumulative sum
-// sequentially (double accumulator, as torch's CPU cumsum).  The token is handed to the greedy
+// sequentially (double accumulator, as torch's CPU cumsum).  A row with more than 256 survivors
+// (hundreds of scores tied at the k-th value) keeps the scores above the tie and the tied tokens of
+// lowest vocabulary index, 256 in all: the one departure from HF, which keeps every tie; it costs
+// the ordinary row nothing (a workgroup-uniform branch on the survivor count).  The token is handed to the greedy
 // finalize kernel as its only argmax partial (nblk = 1), which pads finished rows, records the
 // token, builds the next n-gram ban list and the next input embedding.  No host sync per token:
 // the whole sampled decode is one hipGraph like greedy; the seed lives in device memory so one
@@ -94,7 +97,54 @@ __global__ __launch_bounds__(kThreads) void vcap_sample_kernel(SampleArgs a) {
     }
   }
   __syncthreads();
-  const int nc = min(s_nc, kCand);
+  int nc = s_nc;
+  if (nc > kCand) {
+    // ---- overflow (workgroup-uniform; no real row comes here): fewer than k keys lie above T, so more
+    // than kCand - (k - 1) scores tie at the threshold and HF's support does not fit the LDS slots.
+    // The slots above were handed out in atomic arrival order; redo the selection with a defined
+    // result: every score strictly above the threshold, then the tied tokens of lowest vocabulary
+    // index until kCand slots are full (include/vcap.h, vcap_gpt2_sample).
+    __syncthreads();   // every thread has read s_nc
+    if (t == 0) s_nc = 0;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+      if (fkey(v[i]) > T && v[i] > -INFINITY) {
+        const int slot = atomicAdd(&s_nc, 1);   // < k <= kCand / 2 of them: any order, ranked below
+        c_val[slot] = v[i];
+        c_idx[slot] = t + i * kThreads;
+      }
+    }
+    __syncthreads();
+    const float room = (float)(kCand - s_nc);
+    // X = the largest index bound with at most `room` tied tokens below it (bit by bit, as T above);
+    // the ties outnumber the room, so exactly `room` of them have an index < X
+    int X = 0;
+    for (int b = 15; b >= 0; --b) {   // V <= 50 * 1024 < 2^16
+      const int cand = X | (1 << b);
+      float c = 0.f;
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) c += (fkey(v[i]) == T && t + i * kThreads < cand) ? 1.f : 0.f;
+      c = wave_sum(c);
+      const int buf = b & 1;
+      if (lane == 0) s_cnt[buf][wave] = c;
+      __syncthreads();
+      float tot = 0.f;
+#pragma unroll
+      for (int w = 0; w < kThreads / 64; ++w) tot += s_cnt[buf][w];
+      if (tot <= room) X = cand;
+    }
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+      if (fkey(v[i]) == T && t + i * kThreads < X) {
+        const int slot = atomicAdd(&s_nc, 1);
+        c_val[slot] = v[i];
+        c_idx[slot] = t + i * kThreads;
+      }
+    }
+    __syncthreads();
+    nc = kCand;
+  }
   // ---- ascending order by rank (ties by vocabulary index)
   if (t < nc) {
     const float x = c_val[t];
