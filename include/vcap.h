@@ -33,6 +33,7 @@
  *   vcap_ip_index_convert / vcap_ip_search
  *                           faiss.normalize_L2 + IndexFlatIP.add (scripts/build_index.py:40-42) and
  *                           index.search (scripts/query_video.py:61-75, 127)
+ *   vcap_text_encode        ViTTextAlignModel.encode_text (src/models/vit_text_align.py:67-79)
  */
 #ifndef VCAP_H_
 #define VCAP_H_
@@ -440,6 +441,47 @@ int vcap_ip_search(int storage_dtype, const void* db, int64_t n, int dim, const 
                    void* stream);
 int vcap_ip_search_slab_rows(void);
 int vcap_ip_search_workgroups(int64_t n, int max_blocks);
+
+/* ---- text tower (added within ABI v16: new symbols and structs only): ViTTextAlignModel.encode_text
+ *      (src/models/vit_text_align.py:67-79) - nn.Embedding -> nn.TransformerEncoder of post-LN ReLU
+ *      nn.TransformerEncoderLayer(batch_first) -> mean over the positions whose id != pad_id (count
+ *      clamped to >= 1) -> txt_proj -> F.normalize (eps 1e-12).  As in the reference, the encoder gets no
+ *      key-padding mask: pad positions are ordinary keys and queries and only the pool leaves them out; the
+ *      pad row of the table is gathered as stored; an all-pad caption comes out as normalize(proj_b).
+ *        ids         device [B][L]; an id outside [0, vocab) reads nothing and makes that caption's
+ *                    embedding (and its hidden_out rows) NaN, no other caption's
+ *        out         device [B][proj_dim] f32, unit rows
+ *        hidden_out  optional device [B][L][dim] f32: the encoder output before the pool
+ *      Limits (refused before any launch): dim % 128 == 0, dim <= 1024, n_head * 64 == dim; ffn % 128 == 0,
+ *      ffn <= 4096; proj_dim % 64 == 0, 64 <= proj_dim <= 1024; 1 <= L <= 64, B * L <= vcap_gpt2_max_rows();
+ *      emb, proj_w and the workspace 16-byte aligned (VCAP_E_UNSUPPORTED).  Null pointers, a dtype other
+ *      than VCAP_DT_F32 / VCAP_DT_BF16, a pad_id outside [0, vocab), n_layer < 0 and B < 1: VCAP_E_ARG.
+ *      A short workspace: VCAP_E_WORKSPACE.
+ *      About 2 + 7 * n_layer launches on `stream`; deterministic (fixed reduction orders, no float
+ *      atomics: two calls on the same inputs give the same bits, with or without hidden_out); not
+ *      graph-captured; leaves no state.  vcap_text_workspace_bytes returns 0 outside the limits. ---- */
+typedef struct vcap_text_layer {      /* projection weights rows-packed by vcap_rows_pack, biases / LN f32 */
+  const void* in_w;  const float* in_b;   /* [3E, E] self_attn.in_proj_*   */
+  const void* out_w; const float* out_b;  /* [E, E]  self_attn.out_proj.*  */
+  const float* ln1_g; const float* ln1_b;
+  const void* fc1_w; const float* fc1_b;  /* [F, E]  linear1 */
+  const void* fc2_w; const float* fc2_b;  /* [E, F]  linear2 */
+  const float* ln2_g; const float* ln2_b;
+} vcap_text_layer;
+typedef struct vcap_text_desc {
+  int dtype;                  /* VCAP_DT_F32 | VCAP_DT_BF16: GEMV operands, q/k/v, activations.  Residual stream,
+                                 LayerNorm, softmax, pool, projection and normalisation are f32 in both. */
+  int vocab, dim, n_layer, n_head, ffn, proj_dim, pad_id;
+  float ln_eps;               /* 1e-5 */
+  const float* emb;           /* [vocab, dim] f32 */
+  const float* proj_w; const float* proj_b;   /* [proj_dim, dim], [proj_dim] f32 */
+  const vcap_text_layer* layers;              /* host array of n_layer entries; may be NULL when n_layer == 0 */
+} vcap_text_desc;
+size_t vcap_text_workspace_bytes(const vcap_text_desc* d, int B, int L);
+int vcap_text_encode(const vcap_text_desc* d, const int* ids /* device [B][L] */, int B, int L,
+                     float* out /* device [B][proj_dim], unit rows */,
+                     float* hidden_out /* optional device [B][L][dim]: the encoder output before the pool */,
+                     void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- live kernel timing for the benchmark's roofline (sites: "vit.qkv", "vit.attention",
  *      "vit.proj", "vit.fc1", "vit.fc2"): events are recorded around each launch of the site on

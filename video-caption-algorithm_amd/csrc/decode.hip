@@ -177,6 +177,8 @@ VCAP_DEV void rows_epilogue(const RowsGemmArgs& a, int m0, const float (*red)[MT
       if (ok) ((T*)a.out)[(long)m * a.ldo + n] = Num<T>::from_f(gelu_tanh(v));
     } else if constexpr (EPI == EPI_STORE) {
       if (ok) ((T*)a.out)[(long)m * a.ldo + n] = Num<T>::from_f(v);
+    } else if constexpr (EPI == EPI_RELU) {
+      if (ok) ((T*)a.out)[(long)m * a.ldo + n] = Num<T>::from_f(fmaxf(v, 0.f));
     } else if constexpr (EPI == EPI_LSE) {
       if (m < M) {
         if (n < N) a.logits_raw[(long)m * N + n] = v;
@@ -1498,6 +1500,8 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
   if (pro == PRO_LN && epi == EPI_QKV) { VCAP_ROWS_NT(TT, PRO_LN, EPI_QKV) }                \
   if (pro == PRO_LN && epi == EPI_GELU) { VCAP_ROWS_NT(TT, PRO_LN, EPI_GELU) }              \
   if (pro == PRO_DIRECT && epi == EPI_RESID) { VCAP_ROWS_NT(TT, PRO_DIRECT, EPI_RESID) }    \
+  if (pro == PRO_DIRECT && epi == EPI_STORE && ntb == 1) { VCAP_ROWS(TT, PRO_DIRECT, EPI_STORE, 1) } \
+  if (pro == PRO_DIRECT && epi == EPI_RELU && ntb == 1) { VCAP_ROWS(TT, PRO_DIRECT, EPI_RELU, 1) }   \
   if (pro == PRO_LN && epi == EPI_LOGITS) { VCAP_ROWS(TT, PRO_LN, EPI_LOGITS, 4) }            \
   if (pro == PRO_LN && epi == EPI_LSE) { VCAP_ROWS(TT, PRO_LN, EPI_LSE, 4) }
   if (dt == VCAP_DT_BF16) {

@@ -29,7 +29,8 @@ struct GemmEpi {
 enum { PRO_LN = 0, PRO_DIRECT = 1 };
 // EPI_LSE: raw logits -> logits_raw + per-workgroup (max, sum exp(x - max)) partials per row
 // (part_val / part_sum): the log_softmax statistics of beam search
-enum { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3, EPI_STORE = 4, EPI_LSE = 5 };
+// EPI_STORE / EPI_RELU: T [M, ldo] = acc + bias / max(acc + bias, 0) (the text tower's in_proj and linear1)
+enum { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3, EPI_STORE = 4, EPI_LSE = 5, EPI_RELU = 6 };
 
 struct RowsGemmArgs {
   const void* x;  // PRO_LN: f32 residual rows; PRO_DIRECT: T rows
@@ -40,7 +41,7 @@ struct RowsGemmArgs {
   const void* w;  // rows-packed T weights of a [N, K] matrix (vcap_rows_pack_dispatch)
   const float* bias;
   int M, N, K;
-  void* out;  // RESID: f32 [M, ldo] (+=); GELU/STORE: T [M, ldo]
+  void* out;  // RESID: f32 [M, ldo] (+=); GELU/STORE/RELU: T [M, ldo]
   long ldo;
   // QKV scatter into the paged cache
   void* q_out;            // T [M, E]
@@ -249,6 +250,19 @@ hipError_t vcap_ip_search_dispatch(int dt, const void* db, long n, int dim, cons
 hipError_t vcap_l2_normalize_dispatch(const float* x, long ldx, float* y, long ldy, int rows, int dim, float eps,
                                       int eps_mode, hipStream_t s);
 hipError_t vcap_ip_convert_dispatch(int dt, const float* x, long ldx, long rows, int dim, void* dst, hipStream_t s);
+
+// ---- text tower (csrc/text_encoder.hip): M = B * L rows of E = 64 H features, L <= 64 ----
+// x (f32) and xt (T) [M, E] = emb[ids]; an id outside [0, vocab) gives a NaN row
+hipError_t vcap_text_gather_dispatch(int dt, const int* ids, int M, const float* emb, int vocab, int E, float* x,
+                                     void* xt, hipStream_t s);
+// qkv T [M, 3E] (q | k | v) -> out T [M, E]: softmax(q k^T / 8) v per (caption, head), no mask
+hipError_t vcap_text_attention_dispatch(int dt, const void* qkv, void* out, int B, int L, int H, hipStream_t s);
+// x <- LayerNorm(x) in place (f32) and its T copy xt; E % 128 == 0, E <= 1024
+hipError_t vcap_text_resid_ln_dispatch(int dt, float* x, void* xt, const float* gamma, const float* beta, int M, int E,
+                                       float eps, hipStream_t s);
+// out [B, P] = normalize(pw . mean over ids != pad of x + pb), eps 1e-12; P % 64 == 0, 64 <= P <= 1024
+hipError_t vcap_text_pool_dispatch(const float* x, const int* ids, int pad_id, int B, int L, int E, const float* pw,
+                                   const float* pb, int P, float* out, hipStream_t s);
 
 // JPEG frame decode (jpeg.hip): header of one baseline image, workspace of n same-shape images,
 // host entropy decode + device IDCT / upsampling / colour conversion into uint8 [n, H, W, 3].

@@ -77,6 +77,17 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", C.c_double), ("seed", C.c_uint64)]
 
 
+class TextLayer(C.Structure):
+    _fields_ = [("in_w", vp), ("in_b", vp), ("out_w", vp), ("out_b", vp), ("ln1_g", vp), ("ln1_b", vp),
+                ("fc1_w", vp), ("fc1_b", vp), ("fc2_w", vp), ("fc2_b", vp), ("ln2_g", vp), ("ln2_b", vp)]
+
+
+class TextDesc(C.Structure):
+    _fields_ = [("dtype", i32), ("vocab", i32), ("dim", i32), ("n_layer", i32), ("n_head", i32), ("ffn", i32),
+                ("proj_dim", i32), ("pad_id", i32), ("ln_eps", f32), ("emb", vp), ("proj_w", vp), ("proj_b", vp),
+                ("layers", C.POINTER(TextLayer))]
+
+
 # name -> (restype, argtypes); every symbol include/vcap.h declares
 SIGNATURES = {
     "vcap_last_error": (C.c_char_p, []),
@@ -136,6 +147,8 @@ SIGNATURES = {
     "vcap_ip_search": (i32, [i32, vp, i64, i32, vp, i32, i32, vp, vp, vp, sz, i32, vp]),
     "vcap_ip_search_slab_rows": (i32, []),
     "vcap_ip_search_workgroups": (i32, [i64, i32]),
+    "vcap_text_workspace_bytes": (sz, [C.POINTER(TextDesc), i32, i32]),
+    "vcap_text_encode": (i32, [C.POINTER(TextDesc), vp, i32, i32, vp, vp, vp, sz, vp]),
     "vcap_probe_enable": (i32, [C.c_char_p, i32]),
     "vcap_probe_read": (i32, [C.c_char_p, fp, C.POINTER(C.c_int)]),
     "vcap_probe_read_launches": (i32, [C.c_char_p, fp, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]),

@@ -10,11 +10,15 @@ query_video.py, eval_retrieval.py over src/models/vit_text_align.py::encode_vide
     tensor of f32 or bf16 rows searched exactly by vcap_ip_search.  The FAISS file format is not
     reproduced: `save` writes vectors.npy + index.json (+ the reference's meta.json).
   * `retrieval_metrics` = the Recall@k / MRR loop of eval_retrieval.py:32-54.
+  * `HipTextEmbedder.encode_text` = ViTTextAlignModel.encode_text (vit_text_align.py:67-79): one
+    vcap_text_encode call per chunk of captions; `HipAlignModel` = the model's forward over both towers.
+    A caption query searches the same index a clip query does (scripts/query_text.py).
 
 There is no torch fallback: a CPU tensor is moved to the index's device, and the search is the kernel.
 """
 from __future__ import annotations
 
+import ctypes as C
 import json
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence
@@ -281,3 +285,151 @@ class HipVideoEmbedder:
         """video [B, T, 3, H, W] f32 on the device -> [B, video_dim] f32, unit rows."""
         enc, _ = self.encoder.encode(video)
         return l2_normalize(enc, F_NORMALIZE_EPS, 0, out=enc)
+
+
+# ---- text tower: ViTTextAlignModel.encode_text (vit_text_align.py:67-79) through vcap_text_encode
+TEXT_MAX_LEN = 64
+_TEXT_DTYPE = {"f32": (N.DT_F32, torch.float32), "bf16": (N.DT_BF16, torch.bfloat16)}
+
+
+def text_tower_state_dict(state) -> Dict[str, np.ndarray]:
+    """The txt_* entries (txt_emb, txt_enc.layers.*, txt_proj) of an alignment-model state dict as f32
+    numpy, names unchanged; the dict bare or under {"model_state": ...}."""
+    if isinstance(state, dict) and "model_state" in state:
+        state = state["model_state"]
+    out: Dict[str, np.ndarray] = {}
+    for k, v in state.items():
+        if not k.startswith("txt_"):
+            continue
+        if hasattr(v, "detach"):
+            v = v.detach().float().cpu().numpy()
+        out[k] = np.ascontiguousarray(v, dtype=np.float32)
+    return out
+
+
+class HipTextEmbedder:
+    """ViTTextAlignModel.encode_text on the HIP path: one vcap_text_encode call per chunk of captions.
+
+    The reference's text side is never autocast, so f32 is the default; "bf16" rounds the GEMV operands,
+    the stored q/k/v, the attention output and the ReLU output to bf16 and keeps the rest f32."""
+
+    def __init__(self, sd: Dict[str, np.ndarray], pad_id: int, nhead: int = 8, dtype: str = "f32", device="cuda"):
+        if dtype not in _TEXT_DTYPE:
+            raise ValueError(f"dtype must be one of {sorted(_TEXT_DTYPE)}, got {dtype!r}")
+        sd = text_tower_state_dict(sd)
+        for k in ("txt_emb.weight", "txt_proj.weight", "txt_proj.bias"):
+            if k not in sd:
+                raise ValueError(f"state dict has no {k}: not an alignment-model text tower")
+        self.vocab, self.dim = (int(v) for v in sd["txt_emb.weight"].shape)
+        self.proj_dim = int(sd["txt_proj.weight"].shape[0])
+        if sd["txt_proj.weight"].shape[1] != self.dim:
+            raise ValueError("txt_proj.weight does not match txt_emb.weight's width")
+        if nhead <= 0 or self.dim != 64 * nhead:
+            raise ValueError(f"dim / nhead must be 64 (dim {self.dim}, nhead {nhead}): the kernels' head width")
+        if not 0 <= int(pad_id) < self.vocab:
+            raise ValueError(f"pad_id {pad_id} outside the vocabulary of {self.vocab}")
+        pre = "txt_enc.layers."
+        self.n_layer = 1 + max((int(k[len(pre):].split(".")[0]) for k in sd if k.startswith(pre)), default=-1)
+        self.ffn = int(sd[pre + "0.linear1.weight"].shape[0]) if self.n_layer else 4 * self.dim
+        self.pad_id, self.nhead, self.dtype, self.device = int(pad_id), int(nhead), dtype, torch.device(device)
+        self.dt, tdt = _TEXT_DTYPE[dtype]
+        self._keep: List[torch.Tensor] = []
+        dev = self.device
+
+        def f32(k):
+            t = torch.from_numpy(sd[k]).to(dev).contiguous()
+            self._keep.append(t)
+            return t
+
+        def packed(k):  # [N, K] Linear weight -> operand dtype -> rows-packed (vcap_rows_pack)
+            w = torch.from_numpy(sd[k]).to(dev).to(tdt).contiguous()
+            rows, kk = w.shape
+            nbytes = int(N.lib().vcap_rows_packed_bytes(self.dt, rows, kk))
+            if nbytes == 0:
+                raise ValueError(f"cannot pack {k} {tuple(w.shape)}")
+            p = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            N.check(N.lib().vcap_rows_pack(self.dt, w.data_ptr(), w.stride(0), rows, kk, p.data_ptr(), _stream(dev)),
+                    "vcap_rows_pack")
+            self._keep.append(p)
+            return p
+
+        self.layers = (N.TextLayer * max(self.n_layer, 1))()
+        for i in range(self.n_layer):
+            b, ly = f"{pre}{i}.", self.layers[i]
+            ly.in_w, ly.in_b = packed(b + "self_attn.in_proj_weight").data_ptr(), f32(b + "self_attn.in_proj_bias").data_ptr()
+            ly.out_w, ly.out_b = packed(b + "self_attn.out_proj.weight").data_ptr(), f32(b + "self_attn.out_proj.bias").data_ptr()
+            ly.ln1_g, ly.ln1_b = f32(b + "norm1.weight").data_ptr(), f32(b + "norm1.bias").data_ptr()
+            ly.fc1_w, ly.fc1_b = packed(b + "linear1.weight").data_ptr(), f32(b + "linear1.bias").data_ptr()
+            ly.fc2_w, ly.fc2_b = packed(b + "linear2.weight").data_ptr(), f32(b + "linear2.bias").data_ptr()
+            ly.ln2_g, ly.ln2_b = f32(b + "norm2.weight").data_ptr(), f32(b + "norm2.bias").data_ptr()
+        self.desc = N.TextDesc(dtype=self.dt, vocab=self.vocab, dim=self.dim, n_layer=self.n_layer, n_head=self.nhead,
+                               ffn=self.ffn, proj_dim=self.proj_dim, pad_id=self.pad_id, ln_eps=1e-5,
+                               emb=f32("txt_emb.weight").data_ptr(), proj_w=f32("txt_proj.weight").data_ptr(),
+                               proj_b=f32("txt_proj.bias").data_ptr(), layers=self.layers)
+        self.max_rows = int(N.lib().vcap_gpt2_max_rows())
+        self._ws: Optional[torch.Tensor] = None
+        torch.cuda.synchronize(dev)   # packing ran on the current stream; encodes may use others
+
+    @classmethod
+    def from_state_dict(cls, sd, pad_id: int, nhead: int = 8, dtype: str = "f32", device="cuda") -> "HipTextEmbedder":
+        return cls(sd, pad_id, nhead, dtype, device)
+
+    def _ids(self, ids) -> torch.Tensor:
+        """[B, L] or [L] ids (list, numpy, torch) -> int32 [B, L] on the device.  Ids that arrive on the host
+        are range-checked here; a device tensor is not read back (the kernel turns a bad id into NaN)."""
+        on_device = isinstance(ids, torch.Tensor) and ids.is_cuda
+        t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+        if t.dim() == 1:
+            t = t[None]
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"ids must be integers of shape [B, L] or [L], got {tuple(t.shape)} {t.dtype}")
+        if t.shape[1] > TEXT_MAX_LEN:
+            raise ValueError(f"captions of {t.shape[1]} ids: the text tower takes at most {TEXT_MAX_LEN}")
+        if not on_device and (int(t.min()) < 0 or int(t.max()) >= self.vocab):
+            raise ValueError(f"token id outside [0, {self.vocab})")
+        if on_device and t.dtype != torch.int32:
+            t = t.clamp(-1, self.vocab)     # a wide id must not wrap into the vocabulary in the int32 cast
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def encode_text(self, ids, return_hidden: bool = False):
+        """ids [B, L] or [L] -> [B, proj_dim] f32 unit rows on the device (and, on request, the encoder
+        output [B, L, dim] before the pool).  Batches of more than max_rows / L captions go in chunks."""
+        t = self._ids(ids)
+        B, L = t.shape
+        out = torch.empty(B, self.proj_dim, dtype=torch.float32, device=self.device)
+        hidden = torch.empty(B, L, self.dim, dtype=torch.float32, device=self.device) if return_hidden else None
+        lib, per = N.lib(), max(1, self.max_rows // L)
+        for s in range(0, B, per):
+            n = min(per, B - s)
+            need = int(lib.vcap_text_workspace_bytes(C.byref(self.desc), n, L))
+            if need == 0:
+                raise N.VcapError(f"vcap_text_workspace_bytes refused B={n}, L={L}: "
+                                  f"{(lib.vcap_last_error() or b'').decode()}")
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            N.check(lib.vcap_text_encode(C.byref(self.desc), t[s:s + n].data_ptr(), n, L, out[s:s + n].data_ptr(),
+                                         N.ptr(hidden[s:s + n]) if return_hidden else None, self._ws.data_ptr(),
+                                         self._ws.numel(), _stream(self.device)), "vcap_text_encode")
+        return (out, hidden) if return_hidden else out
+
+
+class HipAlignModel:
+    """ViTTextAlignModel's forward surface over the two HIP towers (inference only)."""
+
+    def __init__(self, video_embedder: HipVideoEmbedder, text_embedder: HipTextEmbedder):
+        self.video_embedder, self.text_embedder = video_embedder, text_embedder
+
+    def encode_video(self, video: torch.Tensor) -> torch.Tensor:
+        return self.video_embedder.encode_video(video)
+
+    def encode_text(self, ids) -> torch.Tensor:
+        return self.text_embedder.encode_text(ids)
+
+    def forward(self, video: torch.Tensor, ids) -> torch.Tensor:
+        """nn.CosineEmbeddingLoss()(encode_video, encode_text, ones) (vit_text_align.py:81-86), computed
+        in torch on the device from the two embeddings."""
+        v, t = self.encode_video(video), self.encode_text(ids)
+        target = torch.ones(v.shape[0], device=v.device)
+        return torch.nn.functional.cosine_embedding_loss(v, t, target)
+
+    __call__ = forward
