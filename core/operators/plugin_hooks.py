@@ -72,5 +72,11 @@ for _h in (
                "vcap_ip_index_convert"),
     PluginHook("flat_ip_search", "scripts/query_video.py:127 faiss.IndexFlatIP.search", "HipFlatIPSearch",
                "vcap_ip_search"),
+    PluginHook("ivf_flat_train", "scripts/build_index_with_captions.py:38-41 faiss.IndexIVFFlat.train (k-means update)",
+               "HipIVFCentroidUpdate", "vcap_ivf_centroid_update"),
+    PluginHook("ivf_flat_add", "scripts/build_index_with_captions.py:44 faiss.IndexIVFFlat.add (coarse assignment)",
+               "HipIVFAssign", "vcap_ivf_assign"),
+    PluginHook("ivf_flat_search", "faiss.IndexIVFFlat.search with METRIC_INNER_PRODUCT over nprobe lists",
+               "HipIVFFlatSearch", "vcap_ivf_search"),
 ):
     register_plugin_hook(_h)

@@ -33,6 +33,9 @@
  *   vcap_ip_index_convert / vcap_ip_search
  *                           faiss.normalize_L2 + IndexFlatIP.add (scripts/build_index.py:40-42) and
  *                           index.search (scripts/query_video.py:61-75, 127)
+ *   vcap_ivf_assign / vcap_ivf_centroid_update / vcap_ivf_search
+ *                           faiss.IndexIVFFlat train / add / search with METRIC_INNER_PRODUCT
+ *                           (build_faiss of scripts/build_index_with_captions.py:33-45)
  *   vcap_text_encode        ViTTextAlignModel.encode_text (src/models/vit_text_align.py:67-79)
  */
 #ifndef VCAP_H_
@@ -441,6 +444,83 @@ int vcap_ip_search(int storage_dtype, const void* db, int64_t n, int dim, const 
                    void* stream);
 int vcap_ip_search_slab_rows(void);
 int vcap_ip_search_workgroups(int64_t n, int max_blocks);
+
+/* ---- IVF-Flat inner-product index (added within ABI v16: new symbols only): the reference's
+ *      faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) of
+ *      scripts/build_index_with_captions.py (--index_type IVF_FLAT --nlist 50): a coarse quantiser over
+ *      nlist centroids, the stored rows grouped into nlist inverted lists, and a search that scans the
+ *      nprobe lists whose centroids score best.  As for the flat search: device pointers only, nothing
+ *      allocates or synchronises, no float atomics, no spinning, safe inside a caller's capture.
+ *      Common limits (VCAP_E_UNSUPPORTED before any launch): dim % 64 == 0 and 64 <= dim <= 1024;
+ *      1 <= nlist <= 1048576; row counts below 2^31; f32 rows and centroids 16-byte aligned with row
+ *      strides in whole 16-byte vectors.  Null pointers and negative sizes: VCAP_E_ARG.
+ *
+ *      vcap_ivf_assign: rows f32 [n, dim] (row stride ldx), centroids f32 [nlist, dim] contiguous ->
+ *        assign int32 [n] and, where score is not null, score f32 [n].  One launch reads the rows once: a
+ *        workgroup stages up to 64 rows and walks the centroid tiles on the f32-input MFMA with a running
+ *        arg-max per row.
+ *        Contract: the score of (row, centroid) has the bits vcap_ip_search(db = centroids, queries = row)
+ *        returns (the same fma chain over the same element permutation, the same operand roles).  The
+ *        winner is the largest score, the lowest centroid id on equal scores (+0 and -0 compare equal);
+ *        a NaN score never wins; a row whose scores are all NaN gets assign -1 and score -inf.  So
+ *        assign / score equal the k = 1 output of vcap_ip_search over the centroids, and a stored f32
+ *        vector used as a query probes its own list first.
+ *      vcap_ivf_centroid_update: one spherical k-means update.  order int64 [n]: row indices grouped by
+ *        list, ascending within a list; offsets int64 [nlist + 1]: list l owns order[offsets[l],
+ *        offsets[l + 1]) (offsets[0] may exceed 0: leading entries of order belong to no list).
+ *        out [nlist, dim] (out == prev allowed) = the f32 sum of the list's member rows, L2-normalised with
+ *        vcap_l2_normalize's mode-0 arithmetic (eps 1e-12).  On unit rows, arg-max inner product against
+ *        unit centroids is the arg-min L2 assignment FAISS trains with.  An empty list keeps its previous
+ *        centroid (FAISS splits a large cluster instead; this library does not).
+ *        Order of summation: members [c * R, (c + 1) * R) of a list (R = vcap_ivf_chunk_rows() = 512) are
+ *        added in order by one wave starting from 0, and the chunks' partial sums are added in chunk order
+ *        by a second kernel.  A centroid's bits depend on its member rows in `order` order only - not on
+ *        the other lists, the grid or a CU mask.  An index in order outside [0, n) is skipped.
+ *        Workspace (16-byte aligned): vcap_ivf_centroid_update_workspace_bytes(n, nlist, dim) =
+ *        (n / R + nlist + 1) rows of dim f32, rounded up to 256 bytes; 0 outside the limits.
+ *      vcap_ivf_search: rows [ntotal, dim] VCAP_DT_F32 or VCAP_DT_BF16, grouped by list; ids int64
+ *        [ntotal] (each row's original id, unique, 0 <= id < 2^31); offsets int64 [nlist + 1] with
+ *        offsets[0] = 0 and offsets[nlist] = ntotal; max_list_len: the host's copy of the longest list's
+ *        length (it sizes the scan grid; rows of a list beyond it are not scanned); out_probes optional
+ *        int64 [nq, nprobe].  Three stages on `stream`:
+ *          (a) coarse: vcap_ip_search's own dispatch over the centroids with k = nprobe -> the probed
+ *              list ids on the device (also into out_probes), best first, -1 where fewer than nprobe
+ *              centroids have a non-NaN score;
+ *          (b) list scan: one workgroup per (query, probe, slice of vcap_ivf_slice_rows() = 512 rows of
+ *              the list), grid ceil(max_list_len / 512) x nprobe x nq; items past their list's end leave
+ *              empty slots.  Each row is scored with the flat scan's chain, so the bits equal
+ *              vcap_ip_search's score of that (row, query, storage dtype); an item keeps its best k keys
+ *              (score, original id) in the workspace.  List starts are not padded: a tile's rows past the
+ *              slice's end read the slice's last row and are dropped, as in the flat scan;
+ *          (c) merge: vcap_ip_search's merge kernel over the items' lists, one workgroup per query.
+ *        Contract: the output is the exact top-k, score descending then id ascending, over the union of
+ *        the rows of the probed lists; id -1 / score -inf where fewer than k exist; a row whose score is
+ *        NaN is never returned.  The output is unique: two calls, grids, max_blocks (it bounds the coarse
+ *        scan's grid only), CU masks or query batchings give the same bits, and with nprobe == nlist (no
+ *        NaN centroid) it is bit-identical to vcap_ip_search over the same vectors with the same ids.
+ *        Limits beyond the common ones: 1 <= k <= 128; 1 <= nprobe <= 128 (nprobe > nlist only adds -1
+ *        probes; callers clamp); 1 <= nq <= 64 and nq * dim <= 16384; max_list_len <= ntotal < 2^31
+ *        (VCAP_E_ARG when it exceeds ntotal); a storage dtype other than F32 / BF16: VCAP_E_ARG; a short
+ *        workspace: VCAP_E_WORKSPACE.  The kernel reads no list whose offsets fall outside [0, ntotal].
+ *      vcap_ivf_search_workspace_bytes: the coarse search's workspace (vcap_ip_search_workspace_bytes(nlist,
+ *        dim, nq, nprobe)) + the probes and their scores + ceil(max_list_len / 512) * nprobe * nq * k
+ *        8-byte key slots, each piece rounded up to 256 bytes; 0 outside the limits.
+ *        Cost: the scan grid, the key workspace and the merge (one workgroup per query walking
+ *        ceil(max_list_len / 512) * nprobe * k slots) all scale with the LONGEST list, not with the lists a
+ *        query probes: with skewed lists most items only write k empty slots and the merge reads them. ---- */
+int vcap_ivf_slice_rows(void);
+int vcap_ivf_chunk_rows(void);
+int vcap_ivf_assign(const float* x, int64_t ldx, int64_t n, const float* centroids, int nlist, int dim, int32_t* assign,
+                    float* score, void* stream);
+size_t vcap_ivf_centroid_update_workspace_bytes(int64_t n, int nlist, int dim);
+int vcap_ivf_centroid_update(const float* x, int64_t ldx, int64_t n, int dim, const int64_t* order,
+                             const int64_t* offsets, int nlist, const float* prev, float* out, void* workspace,
+                             size_t ws_bytes, void* stream);
+size_t vcap_ivf_search_workspace_bytes(int nlist, int64_t max_list_len, int dim, int nq, int nprobe, int k);
+int vcap_ivf_search(int storage_dtype, const void* rows, const int64_t* ids, const int64_t* offsets, int64_t ntotal,
+                    const float* centroids, int nlist, int64_t max_list_len, int dim, const float* queries, int nq,
+                    int nprobe, int k, float* out_scores, int64_t* out_ids, int64_t* out_probes, void* workspace,
+                    size_t ws_bytes, int max_blocks, void* stream);
 
 /* ---- text tower (added within ABI v16: new symbols and structs only): ViTTextAlignModel.encode_text
  *      (src/models/vit_text_align.py:67-79) - nn.Embedding -> nn.TransformerEncoder of post-LN ReLU

@@ -47,6 +47,34 @@ def embed_frames_dir(embedder, frames_dir, args):
     return embedder.encode_video(video)
 
 
+def add_index_type_args(ap) -> None:
+    """The reference's scripts/build_index_with_captions.py index flags."""
+    ap.add_argument("--index_type", choices=["Flat", "IVF_FLAT"], default="Flat")
+    ap.add_argument("--nlist", type=int, default=50, help="clusters of an IVF_FLAT index")
+
+
+def build_index_from(feats, args, normalize: bool):
+    """A Flat or IVF_FLAT index (args.index_type / nlist / storage / device) holding the f32 rows `feats`;
+    an IVF index is trained on the same rows first, as the reference does."""
+    from vcap.retrieval import FlatIPIndex, IVFFlatIPIndex
+    if args.index_type == "IVF_FLAT":
+        index = IVFFlatIPIndex(feats.shape[1], args.nlist, args.storage, args.device, normalize=normalize)
+        index.train(feats)
+    else:
+        index = FlatIPIndex(feats.shape[1], args.storage, args.device, normalize=normalize)
+    index.add(feats)
+    return index
+
+
+def load_index_for_query(directory, args):
+    """load_index plus --nprobe (an IVF index only; 0 keeps the saved value)."""
+    from vcap.retrieval import load_index
+    index = load_index(directory, args.device)
+    if getattr(args, "nprobe", 0) and hasattr(index, "nprobe"):
+        index.nprobe = int(args.nprobe)
+    return index
+
+
 def read_annotations(path):
     """The reference's annotations.json: a list of {"video_id", "frames_dir", "captions": [...]}."""
     anns = json.loads(Path(path).read_text("utf-8"))

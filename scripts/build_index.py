@@ -1,7 +1,8 @@
 """Flat inner-product index over extracted features (the reference's scripts/build_index.py): the
 <video_id>.npy rows of the annotation records that have one, L2-normalised on add (faiss.normalize_L2),
 with meta.json = [{"video_id", "caption"}] carrying each record's first caption.  The index directory
-holds vectors.npy + index.json + meta.json; the FAISS binary format is not reproduced.
+holds vectors.npy + index.json + meta.json; the FAISS binary format is not reproduced.  --index_type IVF_FLAT
+--nlist N (the flags of the reference's scripts/build_index_with_captions.py) builds an IVFFlatIPIndex instead.
 
     python -m scripts.build_index --features features --annotations ann.json --out_dir index
 """
@@ -22,12 +23,13 @@ def parse(argv=None):
     ap.add_argument("--out_dir", required=True)
     ap.add_argument("--storage", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--device", default="cuda")
+    common.add_index_type_args(ap)
     return ap.parse_args(argv)
 
 
 def main(argv=None) -> int:
     args = parse(argv)
-    from vcap.retrieval import FlatIPIndex, first_caption
+    from vcap.retrieval import first_caption
     feats, metas = [], []
     for rec in common.read_annotations(args.annotations):
         fpath = Path(args.features) / f"{rec['video_id']}.npy"
@@ -38,9 +40,9 @@ def main(argv=None) -> int:
     if not feats:
         raise SystemExit(f"[ERROR] no features of {args.annotations} under {args.features}")
     feats = np.stack(feats).astype("float32")
-    print(f"[INFO] Building flat-IP index with {len(feats)} vectors, dim={feats.shape[1]}")
-    index = FlatIPIndex(feats.shape[1], args.storage, args.device, normalize=True)
-    index.add(feats)
+    kind = "flat-IP" if args.index_type == "Flat" else f"IVF-flat-IP (nlist={args.nlist})"
+    print(f"[INFO] Building {kind} index with {len(feats)} vectors, dim={feats.shape[1]}")
+    index = common.build_index_from(feats, args, normalize=True)
     index.metadata = metas
     index.save(args.out_dir)
     print(f"[OK] index -> {Path(args.out_dir) / 'vectors.npy'}")

@@ -20,6 +20,7 @@ def parse(argv=None):
     ap.add_argument("--annotations", required=True)
     ap.add_argument("--index", required=True, help="index directory written by scripts.build_index")
     ap.add_argument("--meta", default="", help="meta.json (default: <index>/meta.json)")
+    ap.add_argument("--nprobe", type=int, default=0, help="lists an IVF_FLAT index scans (0: the saved value)")
     common.add_model_args(ap)
     return ap.parse_args(argv)
 
@@ -27,11 +28,11 @@ def parse(argv=None):
 def main(argv=None):
     args = parse(argv)
     import torch
-    from vcap.retrieval import SCRIPT_L2NORM_EPS, FlatIPIndex, l2_normalize, retrieval_metrics
+    from vcap.retrieval import SCRIPT_L2NORM_EPS, l2_normalize, retrieval_metrics
     idx_dir = Path(args.index)
     meta = json.loads((Path(args.meta) if args.meta else idx_dir / "meta.json").read_text("utf-8"))
     id_list = [m["video_id"] for m in meta]
-    index = FlatIPIndex.load(idx_dir, args.device)
+    index = common.load_index_for_query(idx_dir, args)
     emb = common.load_embedder(args)
     queries, gold = [], []
     for rec in common.read_annotations(args.annotations):

@@ -16,7 +16,7 @@ import json
 import time
 from pathlib import Path
 
-from scripts import _common as common  # noqa: F401  (puts the package on sys.path)
+from scripts import _common as common  # (also puts the package on sys.path)
 
 
 def parse(argv=None):
@@ -29,6 +29,7 @@ def parse(argv=None):
     ap.add_argument("--nhead", type=int, default=8)
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--topk", type=int, default=5)
+    ap.add_argument("--nprobe", type=int, default=0, help="lists an IVF_FLAT index scans (0: the saved value)")
     ap.add_argument("--ids", action="append", default=[], help='one caption as token ids, e.g. "464 3290 318"')
     ap.add_argument("--text", action="append", default=[], help="one caption as text (needs --tokenizer_dir)")
     ap.add_argument("--tokenizer_dir", default="")
@@ -67,14 +68,14 @@ def main(argv=None):
     args = parse(argv)
     caps = caption_ids(args)
     import torch
-    from vcap.retrieval import FlatIPIndex, HipTextEmbedder, meta_caption
+    from vcap.retrieval import HipTextEmbedder, meta_caption
     idx_dir = Path(args.index_dir)
     if not (idx_dir / "index.json").exists():
         raise SystemExit(f"[ERROR] Missing index under {idx_dir}")
     meta_path = Path(args.meta) if args.meta else idx_dir / "meta.json"
     meta = json.loads(meta_path.read_text("utf-8")) if meta_path.exists() else None
     print(f"[INFO] Loading index from {idx_dir}")
-    index = FlatIPIndex.load(idx_dir, args.device)
+    index = common.load_index_for_query(idx_dir, args)
     state = torch.load(args.ckpt, map_location="cpu", weights_only=True)
     try:
         emb = HipTextEmbedder.from_state_dict(state, args.pad_id, args.nhead, args.dtype, args.device)

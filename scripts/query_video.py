@@ -23,6 +23,7 @@ def parse(argv=None):
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--index", required=True, help="index directory written by scripts.build_index")
     ap.add_argument("--meta", default="", help="meta.json (default: <index>/meta.json)")
+    ap.add_argument("--nprobe", type=int, default=0, help="lists an IVF_FLAT index scans (0: the saved value)")
     common.add_model_args(ap)
     return ap.parse_args(argv)
 
@@ -36,7 +37,7 @@ def main(argv=None):
     if not args.frames_dir:
         raise SystemExit("[ERROR] give --frames_dir (a directory of frame_*.jpg)")
     from core.preprocessing.frame_loader import list_frames
-    from vcap.retrieval import SCRIPT_L2NORM_EPS, FlatIPIndex, l2_normalize, meta_caption
+    from vcap.retrieval import SCRIPT_L2NORM_EPS, l2_normalize, meta_caption
     idx_dir = Path(args.index)
     meta_path = Path(args.meta) if args.meta else idx_dir / "meta.json"
     if not (idx_dir / "index.json").exists() or not meta_path.exists():
@@ -44,7 +45,7 @@ def main(argv=None):
     if not list_frames(args.frames_dir):
         raise SystemExit(f"[ERROR] No frames found in {args.frames_dir}")
     print(f"[INFO] Loading index from {idx_dir}")
-    index = FlatIPIndex.load(idx_dir, args.device)
+    index = common.load_index_for_query(idx_dir, args)
     meta = json.loads(meta_path.read_text("utf-8"))
     emb = common.load_embedder(args)
     print("[INFO] Encoding query video ...")

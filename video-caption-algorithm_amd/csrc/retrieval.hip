@@ -23,6 +23,7 @@
 // registers; in the merge the workgroup over an LDS copy).  Nothing depends on arrival order, so the
 // lists - and after the same procedure in the merge kernel, the output - are a function of the key set.
 // No float atomics, no spinning; the only atomics are LDS integer slot counters.
+#include "retrieval_common.h"   // the key, compact_topk and the bf16 widening, shared with ivf.hip
 #include "vcap_common.h"
 #include "vcap_kernels.h"
 
@@ -30,47 +31,14 @@
 
 namespace {
 
-typedef unsigned long long ipkey_t;
-
-constexpr int kThreads = 256;
+constexpr int kThreads = kIpThreads;
 constexpr int kWaveTiles = 2;                                  // 16-row tiles per wave and slab
 constexpr int kSlab = (kThreads / 64) * kWaveTiles * 16;       // rows per workgroup step
 static_assert(kSlab == kIpSlabRows, "vcap_kernels.h kIpSlabRows");
 constexpr int kMergeLoads = 8;                                 // keys per thread and merge round
 constexpr int kMergeCap = kIpMaxK + 2 * kThreads;
 
-VCAP_DEV ipkey_t make_key(float score, unsigned id) {
-  unsigned b = __float_as_uint(score + 0.0f);                  // -0 -> +0: equal scores, equal bits
-  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((ipkey_t)b << 32) | (ipkey_t)(0xFFFFFFFFu - id);
-}
-VCAP_DEV float key_score(ipkey_t k) {
-  const unsigned b = (unsigned)(k >> 32);
-  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
-}
-VCAP_DEV long long key_id(ipkey_t k) { return (long long)(0xFFFFFFFFu - (unsigned)k); }
-
-// The m keys of buf -> their best min(m, k) in descending order in buf[0 ..), *thr = the k-th best where
-// there are k, *cnt = min(m, k).  Every thread of the workgroup calls it with the same arguments, after a
-// barrier that follows the last append; sel is LDS scratch of `room` keys (m never exceeds it by the
-// callers' append rule; the clamp keeps a broken rule from becoming an out-of-bounds access).  Ends with a
-// barrier.
-VCAP_DEV void compact_topk(ipkey_t* buf, ipkey_t* sel, int m, int room, int k, ipkey_t* thr, int* cnt) {
-  m = min(m, room);
-  for (int i = threadIdx.x; i < m; i += kThreads) sel[i] = buf[i];
-  __syncthreads();
-  for (int i = threadIdx.x; i < m; i += kThreads) {
-    const ipkey_t key = sel[i];
-    int rank = 0;
-    for (int j = 0; j < m; ++j) rank += sel[j] > key;
-    if (rank < k) buf[rank] = key;
-    if (rank == k - 1) *thr = key;
-  }
-  if (threadIdx.x == 0) *cnt = min(m, k);
-  __syncthreads();
-}
-
-// The same selection by ONE wave with the keys in registers (the scan kernel: each wave of the workgroup
+// compact_topk's selection by ONE wave with the keys in registers (the scan kernel: each wave of the workgroup
 // compacts other queries' buffers at once, with no workgroup barrier inside).  buf holds m <= kScanRoom keys
 // (m wave-uniform); lane l owns keys l, l + 64, ...; every key is broadcast with v_readlane and each lane
 // counts, per key it owns, the keys above it.  All loads of buf precede the first store (the ranks depend on
@@ -107,10 +75,6 @@ VCAP_DEV void wave_compact_topk(ipkey_t* buf, int m, int k, ipkey_t* thr, int* c
     }
   if (lane == 0) *cnt = min(m, k);
 }
-
-// the two f32 fragments of a 16-byte load of 8 bf16 (element 2 i in the low half of dword i)
-VCAP_DEV u32x4 widen_lo(u32x4 v) { return (u32x4){v.x << 16, v.x & 0xFFFF0000u, v.y << 16, v.y & 0xFFFF0000u}; }
-VCAP_DEV u32x4 widen_hi(u32x4 v) { return (u32x4){v.z << 16, v.z & 0xFFFF0000u, v.w << 16, v.w & 0xFFFF0000u}; }
 
 // grid.x workgroups; workgroup w takes slabs w, w + grid.x, ...  ws: [grid.x][nq][cap] keys.
 template <bool BF16, int QT>
@@ -375,6 +339,14 @@ hipError_t vcap_ip_search_dispatch(int dt, const void* db, long n, int dim, cons
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// the merge kernel alone, over `lists` sorted lists ws[list][query][0, k) of row stride cap (the IVF list scan's)
+hipError_t vcap_ip_merge_dispatch(const void* ws, int lists, int nq, int cap, int k, float* out_scores,
+                                  long long* out_ids, hipStream_t s) {
+  hipLaunchKernelGGL(vcap_ip_merge_kernel, dim3(nq), dim3(kThreads), 0, s, (const ipkey_t*)ws, lists, nq, cap, k,
+                     out_scores, out_ids);
+  return hipGetLastError();
 }
 
 hipError_t vcap_l2_normalize_dispatch(const float* x, long ldx, float* y, long ldy, int rows, int dim, float eps,

@@ -250,6 +250,29 @@ hipError_t vcap_ip_search_dispatch(int dt, const void* db, long n, int dim, cons
 hipError_t vcap_l2_normalize_dispatch(const float* x, long ldx, float* y, long ldy, int rows, int dim, float eps,
                                       int eps_mode, hipStream_t s);
 hipError_t vcap_ip_convert_dispatch(int dt, const float* x, long ldx, long rows, int dim, void* dst, hipStream_t s);
+// the flat search's merge alone: the k best of ws[list][query][0, k) (keys, row stride cap) -> the outputs
+hipError_t vcap_ip_merge_dispatch(const void* ws, int lists, int nq, int cap, int k, float* out_scores,
+                                  long long* out_ids, hipStream_t s);
+
+// ---- IVF-Flat index (csrc/ivf.hip): coarse assignment, spherical centroid update, probed list scan ----
+constexpr int kIvfSliceRows = 512;         // rows of one list a scan workgroup takes: an item is (query, probe, slice)
+constexpr int kIvfChunkRows = 512;         // member rows one wave sums in the centroid update
+constexpr int kIvfMaxProbe = 128;
+constexpr int kIvfMaxLists = 1 << 20;
+// assign[r] = the centroid with the largest inner product (lowest id on ties, -1 when every score is NaN),
+// score[r] (optional) that score: the bits vcap_ip_search_dispatch(db = centroids, queries = row) returns
+hipError_t vcap_ivf_assign_dispatch(const float* x, long ldx, long n, const float* centroids, int nlist, int dim,
+                                    int* assign, float* score, hipStream_t s);
+long vcap_ivf_update_slots(long n, int nlist);   // partial-sum rows of the centroid update's workspace
+hipError_t vcap_ivf_centroid_update_dispatch(const float* x, long ldx, long n, int dim, const long long* order,
+                                             const long long* offsets, int nlist, const float* prev, float* out,
+                                             float eps, float* partials, hipStream_t s);
+// probes [nq, nprobe] / probe_scores: the coarse stage's outputs; keys: [nprobe * slices][nq][k] 8-byte slots
+hipError_t vcap_ivf_search_dispatch(int dt, const void* rows, const long long* ids, const long long* offsets, long ntotal,
+                                    const float* centroids, int nlist, long max_list_len, int dim,
+                                    const float* queries, int nq, int nprobe, int k, float* out_scores,
+                                    long long* out_ids, long long* probes, float* probe_scores, void* coarse_ws,
+                                    void* keys, int max_blocks, hipStream_t s);
 
 // ---- text tower (csrc/text_encoder.hip): M = B * L rows of E = 64 H features, L <= 64 ----
 // x (f32) and xt (T) [M, E] = emb[ids]; an id outside [0, vocab) gives a NaN row

@@ -147,6 +147,13 @@ SIGNATURES = {
     "vcap_ip_search": (i32, [i32, vp, i64, i32, vp, i32, i32, vp, vp, vp, sz, i32, vp]),
     "vcap_ip_search_slab_rows": (i32, []),
     "vcap_ip_search_workgroups": (i32, [i64, i32]),
+    "vcap_ivf_slice_rows": (i32, []),
+    "vcap_ivf_chunk_rows": (i32, []),
+    "vcap_ivf_assign": (i32, [vp, i64, i64, vp, i32, i32, vp, vp, vp]),
+    "vcap_ivf_centroid_update_workspace_bytes": (sz, [i64, i32, i32]),
+    "vcap_ivf_centroid_update": (i32, [vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "vcap_ivf_search_workspace_bytes": (sz, [i32, i64, i32, i32, i32, i32]),
+    "vcap_ivf_search": (i32, [i32, vp, vp, vp, i64, vp, i32, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, i32, vp]),
     "vcap_text_workspace_bytes": (sz, [C.POINTER(TextDesc), i32, i32]),
     "vcap_text_encode": (i32, [C.POINTER(TextDesc), vp, i32, i32, vp, vp, vp, sz, vp]),
     "vcap_probe_enable": (i32, [C.c_char_p, i32]),

@@ -197,6 +197,322 @@ class FlatIPIndex:
         return idx
 
 
+MAX_NPROBE = 128
+
+
+def ivf_slice_rows() -> int:
+    """Rows of one list a scan workgroup takes (a work item is (query, probe, slice))."""
+    return int(N.lib().vcap_ivf_slice_rows())
+
+
+def ivf_chunk_rows() -> int:
+    """Member rows one wave sums in the centroid update."""
+    return int(N.lib().vcap_ivf_chunk_rows())
+
+
+def ivf_assign(x: torch.Tensor, centroids: torch.Tensor, want_scores: bool = True):
+    """vcap_ivf_assign: device f32 rows [n, dim] (unit inner stride) against contiguous f32 centroids
+    [nlist, dim] -> (assign int32 [n], score f32 [n] or None): the best centroid by inner product."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.stride(1) != 1:
+        raise ValueError("ivf_assign: expect a device f32 [rows, dim] tensor with unit inner stride")
+    if centroids.dtype != torch.float32 or centroids.dim() != 2 or not centroids.is_contiguous() or \
+            centroids.device != x.device or centroids.shape[1] != x.shape[1]:
+        raise ValueError("ivf_assign: centroids must be contiguous f32 [nlist, dim] on the rows' device")
+    n, dim = x.shape
+    assign = torch.empty(n, dtype=torch.int32, device=x.device)
+    score = torch.empty(n, dtype=torch.float32, device=x.device) if want_scores else None
+    N.check(N.lib().vcap_ivf_assign(x.data_ptr(), x.stride(0) if n > 1 else max(x.stride(0), dim), n,
+                                    centroids.data_ptr(), centroids.shape[0], dim, assign.data_ptr(), N.ptr(score),
+                                    _stream(x.device)), "vcap_ivf_assign")
+    return assign, score
+
+
+def ivf_group(assign: torch.Tensor, nlist: int):
+    """The grouping the centroid update and the index read: assign [n] (list id, or -1) -> (order int64 [n]:
+    row indices by list, ascending within a list, the unassigned rows first; offsets int64 [nlist + 1]).
+    A stable sort plus bincount / cumsum on the device."""
+    a = assign.to(torch.int64)
+    order = torch.sort(a, stable=True).indices
+    counts = torch.bincount(a.clamp_min(0), weights=(a >= 0).to(torch.float64), minlength=nlist).to(torch.int64)
+    offsets = torch.empty(nlist + 1, dtype=torch.int64, device=assign.device)
+    offsets[0] = (a < 0).sum()
+    offsets[1:] = offsets[0] + torch.cumsum(counts, 0)
+    return order.contiguous(), offsets
+
+
+def ivf_centroid_update(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, prev: torch.Tensor,
+                        workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+    """vcap_ivf_centroid_update: the L2-normalised sums of the grouped member rows; an empty list keeps prev's row."""
+    n, dim = x.shape
+    nlist = prev.shape[0]
+    if x.dtype != torch.float32 or x.stride(1) != 1 or not prev.is_contiguous() or prev.dtype != torch.float32 or \
+            order.dtype != torch.int64 or offsets.dtype != torch.int64 or order.numel() != n or \
+            offsets.numel() != nlist + 1 or not order.is_contiguous() or not offsets.is_contiguous():
+        raise ValueError("ivf_centroid_update: f32 rows / centroids, int64 order [n] and offsets [nlist + 1]")
+    lib = N.lib()
+    need = int(lib.vcap_ivf_centroid_update_workspace_bytes(n, nlist, dim))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(prev)
+    N.check(lib.vcap_ivf_centroid_update(x.data_ptr(), x.stride(0) if n > 1 else max(x.stride(0), dim), n, dim,
+                                         order.data_ptr(), offsets.data_ptr(), nlist, prev.data_ptr(), out.data_ptr(),
+                                         workspace.data_ptr(), workspace.numel(),
+                                         _stream(x.device) if stream is None else stream), "vcap_ivf_centroid_update")
+    return out
+
+
+class IVFFlatIPIndex:
+    """faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) on the device (the reference's
+    scripts/build_index_with_captions.py --index_type IVF_FLAT): a coarse quantiser of nlist centroids, the
+    rows grouped into inverted lists, and a search over the nprobe lists whose centroids score best.
+
+    Within the probed lists the search is exact and ordered as FlatIPIndex's (score descending, then id
+    ascending, filler -1 / -inf); with nprobe == nlist it returns FlatIPIndex's bits.  The FAISS file format
+    is not reproduced, and training is spherical k-means without FAISS's splitting of large clusters."""
+
+    def __init__(self, dim: int, nlist: int, storage: str = "f32", device="cuda", normalize: bool = False,
+                 nprobe: int = 1):
+        if storage not in _STORAGE:
+            raise ValueError(f"storage must be one of {sorted(_STORAGE)}, got {storage!r}")
+        if dim % 64 or not 64 <= dim <= 1024:
+            raise ValueError("dim must be a multiple of 64 in 64..1024")
+        if not 1 <= int(nlist) <= 1 << 20:
+            raise ValueError("nlist must be in 1..1048576")
+        if int(nprobe) < 1:
+            raise ValueError("nprobe must be at least 1")
+        self.dim, self.nlist, self.storage, self.device = int(dim), int(nlist), storage, torch.device(device)
+        self.normalize, self.nprobe = bool(normalize), int(nprobe)
+        self.ntotal = 0
+        self.metadata: Optional[List[Dict[str, str]]] = None
+        self.train_objective: List[float] = []        # mean best inner product of each training round's assignment
+        self._dt, self._tdt = _STORAGE[storage]
+        self._centroids: Optional[torch.Tensor] = None
+        self._rows = torch.empty(0, self.dim, dtype=self._tdt, device=self.device)      # grouped by list
+        self._ids = torch.empty(0, dtype=torch.int64, device=self.device)               # original id of each grouped row
+        self._lists = torch.empty(0, dtype=torch.int32, device=self.device)             # list of each grouped row
+        self._offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        self._host_offsets = np.zeros(self.nlist + 1, np.int64)
+        self._ws: Optional[torch.Tensor] = None
+
+    # ---- the coarse quantiser
+    @property
+    def is_trained(self) -> bool:
+        return self._centroids is not None
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        """The coarse centroids [nlist, dim] f32 (a view)."""
+        if self._centroids is None:
+            raise RuntimeError("the index is not trained")
+        return self._centroids
+
+    def set_centroids(self, centroids) -> None:
+        """Install coarse centroids [nlist, dim] trained elsewhere, as given (the index must be empty)."""
+        if self.ntotal:
+            raise RuntimeError("set_centroids on an index that holds rows")
+        c = _f32_rows(centroids, self.device, self.dim)
+        if c.shape[0] != self.nlist:
+            raise ValueError(f"expect [{self.nlist}, {self.dim}] centroids, got {tuple(c.shape)}")
+        self._centroids = c.clone()
+
+    def training_set(self, x, seed: int = 1234, max_points_per_centroid: int = 256):
+        """What train starts from: (the f32 training rows on the device - normalised if the index normalises,
+        subsampled to at most max_points_per_centroid * nlist - and the initial centroids [nlist, dim])."""
+        x = _f32_rows(x, self.device, self.dim)
+        n = x.shape[0]
+        if n < self.nlist:
+            raise ValueError(f"train needs at least nlist = {self.nlist} rows, got {n}")
+        if self.normalize:
+            x = l2_normalize(x, F_NORMALIZE_EPS, 0)
+        rng = np.random.default_rng(seed)
+        cap = max(1, int(max_points_per_centroid)) * self.nlist
+        if n > cap:
+            x = x[torch.from_numpy(rng.permutation(n)[:cap]).to(self.device)].contiguous()
+            n = cap
+        first = torch.from_numpy(np.sort(rng.choice(n, self.nlist, replace=False))).to(self.device)
+        return x, l2_normalize(x[first].contiguous(), F_NORMALIZE_EPS, 0)
+
+    def train(self, x, niter: int = 10, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
+        """Spherical k-means on the device.  One numpy.random.default_rng(seed) draws the subsample (at most
+        max_points_per_centroid * nlist rows) and then nlist distinct rows as the initial centroids
+        (L2-normalised); niter rounds of assign (vcap_ivf_assign) -> group (stable sort) -> update
+        (vcap_ivf_centroid_update) follow.  The same rows and seed give the same centroid bits.
+
+        nprobe = 1, niter = 10 and 256 points per centroid are FAISS's defaults as remembered - FAISS was not
+        available to compare with, and no bit parity with FAISS's centroids is claimed: FAISS minimises L2
+        (on unit rows the same assignment as arg-max inner product against unit centroids) and splits a large
+        cluster to refill an empty one, where this index lets an empty list keep its centroid."""
+        x, cent = self.training_set(x, seed, max_points_per_centroid)
+        n = x.shape[0]
+        need = int(N.lib().vcap_ivf_centroid_update_workspace_bytes(n, self.nlist, self.dim))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        objective = []
+        for _ in range(int(niter)):
+            assign, score = ivf_assign(x, cent)
+            objective.append(torch.where(assign >= 0, score, torch.zeros_like(score)).double().mean())
+            order, offsets = ivf_group(assign, self.nlist)
+            cent = ivf_centroid_update(x, order, offsets, cent, ws)
+        self.train_objective = [float(v) for v in objective]
+        self._centroids = cent
+
+    # ---- the inverted lists
+    @property
+    def vectors(self) -> torch.Tensor:
+        """The stored rows [ntotal, dim] in the storage dtype, grouped by list (a view)."""
+        return self._rows
+
+    @property
+    def ids(self) -> torch.Tensor:
+        """The original id of every grouped row [ntotal] int64."""
+        return self._ids
+
+    def list_sizes(self) -> np.ndarray:
+        return np.diff(self._host_offsets)
+
+    def reset(self) -> None:
+        """Drop the stored rows; the trained centroids stay."""
+        self.ntotal, self.metadata = 0, None
+        self._rows = torch.empty(0, self.dim, dtype=self._tdt, device=self.device)      # not views: the table is freed
+        self._ids = torch.empty(0, dtype=torch.int64, device=self.device)
+        self._lists = torch.empty(0, dtype=torch.int32, device=self.device)
+        self._offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        self._host_offsets = np.zeros(self.nlist + 1, np.int64)
+
+    def add(self, x) -> None:
+        """Rows get the sequential ids ntotal, ntotal + 1, ... (as under FAISS) and join the list of their best
+        centroid; the table is regrouped (stable: ascending id within a list), so add(a); add(b) stores what
+        add(cat(a, b)) stores.  The row is assigned as stored (bf16 storage: after the rounding), so a stored
+        vector used as a query probes its own list first; a row with no non-NaN score goes to list 0.
+
+        Cost: every call concatenates, stable-sorts and gathers the WHOLE table (peak memory about twice the
+        table) and copies the nlist + 1 offsets back to the host, so k small adds cost O(k * ntotal); add in
+        large batches.  Merging into the grouped table instead would keep the same contract; it is not built."""
+        if not self.is_trained:
+            raise RuntimeError("train the index before add")
+        x = _f32_rows(x, self.device, self.dim)
+        rows = x.shape[0]
+        if not rows:
+            return
+        if self.ntotal + rows >= 1 << 31:
+            raise ValueError("ids must stay below 2^31")
+        if self.normalize:
+            x = l2_normalize(x, F_NORMALIZE_EPS, 0)
+        stored = torch.empty(rows, self.dim, dtype=self._tdt, device=self.device)
+        N.check(N.lib().vcap_ip_index_convert(x.data_ptr(), self.dim, rows, self.dim, self._dt, stored.data_ptr(),
+                                              _stream(self.device)), "vcap_ip_index_convert")
+        assign, _ = ivf_assign(stored if self.storage == "f32" else stored.float(), self._centroids, False)
+        lists = torch.cat([self._lists, assign.clamp_min(0)])
+        order = torch.sort(lists.to(torch.int64), stable=True).indices
+        ids = torch.cat([self._ids, torch.arange(self.ntotal, self.ntotal + rows, dtype=torch.int64, device=self.device)])
+        self._rows = torch.cat([self._rows, stored])[order].contiguous()
+        self._ids, self._lists = ids[order].contiguous(), lists[order].contiguous()
+        self._offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        self._offsets[1:] = torch.cumsum(torch.bincount(self._lists.to(torch.int64), minlength=self.nlist), 0)
+        self._host_offsets = self._offsets.cpu().numpy()       # the scan grid is sized from the longest list
+        self.ntotal += rows
+
+    # ---- search
+    def _search(self, q, k: int, max_blocks: int, want_probes: bool):
+        if not self.is_trained:
+            raise RuntimeError("train the index before search")
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in 1..{MAX_K}")
+        q = _f32_rows(q, self.device, self.dim)
+        nq = q.shape[0]
+        nprobe = max(1, min(self.nprobe, self.nlist, MAX_NPROBE))
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        P = torch.empty(nq, nprobe, dtype=torch.int64, device=self.device) if want_probes else None
+        rows = self._rows if self.ntotal else torch.empty(1, self.dim, dtype=self._tdt, device=self.device)
+        ids = self._ids if self.ntotal else torch.zeros(1, dtype=torch.int64, device=self.device)
+        longest = int(np.diff(self._host_offsets).max())
+        lib = N.lib()
+        chunk = min(MAX_NQ, MAX_QUERY_FLOATS // self.dim)
+        for s in range(0, nq, chunk):
+            part = q[s:s + chunk]
+            need = int(lib.vcap_ivf_search_workspace_bytes(self.nlist, longest, self.dim, part.shape[0], nprobe, k))
+            if need == 0:
+                raise N.VcapError(f"vcap_ivf_search_workspace_bytes refused: {(lib.vcap_last_error() or b'').decode()}")
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            N.check(lib.vcap_ivf_search(self._dt, rows.data_ptr(), ids.data_ptr(), self._offsets.data_ptr(), self.ntotal,
+                                        self._centroids.data_ptr(), self.nlist, longest, self.dim, part.data_ptr(),
+                                        part.shape[0], nprobe, k, D[s:s + chunk].data_ptr(), I[s:s + chunk].data_ptr(),
+                                        P[s:s + chunk].data_ptr() if want_probes else None, self._ws.data_ptr(),
+                                        self._ws.numel(), max_blocks, _stream(self.device)), "vcap_ivf_search")
+        return D, I, P
+
+    def search(self, q, k: int, max_blocks: int = 0):
+        """q [nq, dim] (torch or numpy, any nq) -> (D [nq, k] f32, I [nq, k] int64) on the index's device: the
+        exact top-k over the rows of the min(nprobe, nlist) lists each query probes."""
+        D, I, _ = self._search(q, k, max_blocks, False)
+        return D, I
+
+    def probe_lists(self, q) -> torch.Tensor:
+        """The list ids [nq, min(nprobe, nlist)] int64 the search scans for each query, best centroid first
+        (-1 where fewer centroids have a non-NaN score), as the search call itself reports them.  For tests and
+        diagnostics: it costs a whole search call (coarse stage, list scan and merge at k = 1), not the coarse
+        stage alone."""
+        return self._search(q, 1, 0, True)[2]
+
+    # ---- persistence: index.json ("type": "IVF_FLAT") + centroids.npy + vectors.npy (grouped) + ids.npy + offsets.npy
+    def save(self, directory) -> None:
+        if not self.is_trained:
+            raise RuntimeError("train the index before save")
+        d = Path(directory)
+        d.mkdir(parents=True, exist_ok=True)
+        v = self._rows
+        arr = v.cpu().numpy() if self.storage == "f32" else v.view(torch.int16).cpu().numpy().view(np.uint16)
+        np.save(d / "vectors.npy", arr)
+        np.save(d / "centroids.npy", self._centroids.cpu().numpy())
+        np.save(d / "ids.npy", self._ids.cpu().numpy())
+        np.save(d / "offsets.npy", self._host_offsets)
+        (d / "index.json").write_text(json.dumps({"type": "IVF_FLAT", "dim": self.dim, "storage": self.storage,
+                                                  "ntotal": self.ntotal, "normalize": self.normalize,
+                                                  "nlist": self.nlist, "nprobe": self.nprobe}))
+        if self.metadata is not None:
+            write_meta(d / "meta.json", self.metadata)
+
+    @classmethod
+    def load(cls, directory, device="cuda") -> "IVFFlatIPIndex":
+        d = Path(directory)
+        info = json.loads((d / "index.json").read_text())
+        if info.get("type") != "IVF_FLAT":
+            raise ValueError(f"{d} does not hold an IVF_FLAT index")
+        idx = cls(info["dim"], info["nlist"], info["storage"], device, info.get("normalize", False), info.get("nprobe", 1))
+        arr, cent = np.load(d / "vectors.npy"), np.load(d / "centroids.npy")
+        ids, offsets = np.load(d / "ids.npy"), np.load(d / "offsets.npy")
+        n = info["ntotal"]
+        if arr.shape != (n, idx.dim) or cent.shape != (idx.nlist, idx.dim) or ids.shape != (n,) or \
+                offsets.shape != (idx.nlist + 1,) or offsets[0] != 0 or offsets[-1] != n or (np.diff(offsets) < 0).any():
+            raise ValueError(f"the arrays under {d} do not match index.json")
+        if n and (np.sort(ids) != np.arange(n)).any():
+            raise ValueError(f"{d / 'ids.npy'} is not a permutation of 0..ntotal-1")
+        idx._centroids = torch.from_numpy(cent.astype(np.float32)).to(idx.device).contiguous()
+        t = torch.from_numpy(arr) if info["storage"] == "f32" else torch.from_numpy(arr.view(np.int16)).view(torch.bfloat16)
+        idx._rows = t.to(idx.device).contiguous()              # stored bits, not re-normalised or re-assigned
+        idx._ids = torch.from_numpy(ids.astype(np.int64)).to(idx.device)
+        idx._host_offsets = offsets.astype(np.int64)
+        idx._offsets = torch.from_numpy(idx._host_offsets).to(idx.device)
+        idx._lists = torch.repeat_interleave(torch.arange(idx.nlist, dtype=torch.int32, device=idx.device),
+                                             torch.from_numpy(np.diff(idx._host_offsets)).to(idx.device))
+        idx.ntotal = n
+        if (d / "meta.json").exists():
+            idx.metadata = json.loads((d / "meta.json").read_text("utf-8"))
+        return idx
+
+
+def load_index(directory, device="cuda"):
+    """The index a directory holds: index.json's "type" picks the class; a directory without one is a
+    flat index (everything written before the key existed)."""
+    kind = json.loads((Path(directory) / "index.json").read_text()).get("type", "Flat")
+    if kind == "IVF_FLAT":
+        return IVFFlatIPIndex.load(directory, device)
+    if kind == "Flat":
+        return FlatIPIndex.load(directory, device)
+    raise ValueError(f"unknown index type {kind!r} in {Path(directory) / 'index.json'}")
+
+
 def check_meta(meta) -> List[Dict[str, str]]:
     """The reference's meta.json: a list of {"video_id": str, "caption": str} (build_index.py:31-34)."""
     if not isinstance(meta, list):
