@@ -179,8 +179,9 @@ int vcap_gemm(int in_dtype, int out_dtype, const void* A, int64_t lda, const voi
 /* The in-place residual GEMM of the encoder's class-token-only last block, at the op level:
  *   C[orow(m)][n] += sum_k A[m][k] W[n][k] + bias[n],   orow(m) = G ? (m / G) * Gs + m % G : m
  * with BF16 or F16 operands, f32 C, and a caller workspace (>= 8 * M * N * 4 bytes, 16-byte aligned) for
- * deterministic split-K partials: where the dispatcher runs the 128x128 kernel (few tiles, gemm policy 0
- * or 1) K is split over the largest c <= 8 dividing the K-tile count with >= 3 K-tiles per split, the
+ * deterministic split-K partials: K is split over the largest c <= 8 dividing the K-tile count with >= 3
+ * K-tiles per split (a launch that splits runs the 128x128 kernel under every gemm policy and tile count:
+ * the split count depends on K alone), the
  * partial slabs are summed in split order by a second kernel, and - F16 - the sum + bias is rounded to
  * fp16 there, before the add.  *splits_out (optional) receives c (1: not split).  This is the path
  * vcap_vit_encode takes for attn-proj / fc2 of its last block. */
@@ -262,7 +263,11 @@ int vcap_prefix_project(const float* emb, int B, int video_dim, const vcap_prefi
 size_t vcap_rows_packed_bytes(int dtype, int N, int K);
 int vcap_rows_pack(int dtype, const void* w, int64_t ldw, int N, int K, void* packed, void* stream);
 
-/* ---- fused paths ---- */
+/* ---- fused paths ----
+ * ViT descriptor limits (VCAP_E_UNSUPPORTED before any launch, workspace query 0): head_dim 64, dim <= 1024,
+ * video_dim <= 1024, dim / mlp / kpad multiples of the GEMM K step, a square grid of at most 288 tokens (class
+ * token included) - 33..192 and 225..256 tokens in VCAP_DT_F16 only, the one dtype the generic attention
+ * kernel is built for. */
 size_t vcap_vit_workspace_bytes(const vcap_vit_desc* d, int B, int T);
 int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const float* frames, int B, int T,
                     float* enc_out, float* prefix_out, void* workspace, size_t ws_bytes, void* stream);

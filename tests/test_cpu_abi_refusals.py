@@ -7,7 +7,9 @@ Also pins the four GPT-2 workspace queries, whose carving the entry points share
 Rows marked "isnew" are refusals that came with the shared prompt checks: vcap_gpt2_sample and
 vcap_gpt2_beam_search with no context row (they used to launch on zero rows) and vcap_gpt2_prefill with
 a prompt id outside the vocabulary (it used to embed it).  Greedy and sampling decode have no row for a
-context above 1024: with at most 512 prefill rows and 64 new tokens no call reaches it."""
+context above 1024: with at most 512 prefill rows and 64 new tokens no call reaches it.  The "isnew" rows of
+vcap_vit_encode came with the encoder shape sweep (tests/encoder_shapes.py): shapes check_vit used to accept and
+the encode then failed on after its first launches (-hipErrorInvalidValue from "attention" / "head_prefix")."""
 import ctypes as C
 
 import pytest
@@ -149,6 +151,18 @@ ROWS = [
      "MXFP8 LayerNorm holds rows of <= 1024 in registers"),
     ("vit_encode", dict(desc=dict(image=230)), ARG, "image not divisible by patch"),
     ("vit_encode", dict(desc=dict(image=288)), UNSUP, "more than 288 tokens"),
+    # shapes the encode used to accept and then fail in the middle of (after patchify, the patch GEMM, LayerNorm and
+    # the QKV GEMM, or after the whole encoder): a token count the attention dispatcher serves in fp16 only, in
+    # f32 (65), bf16 (226) and MXFP8 (50); rows the head / prefix kernels cannot hold
+    ("vit_encode", dict(desc=dict(patch=8, image=64)), UNSUP, "vit attention serves 33..192 and 225..256 tokens in fp16 only",
+     "isnew"),
+    ("vit_encode", dict(desc=dict(dtype=N.DT_BF16, image=240)), UNSUP,
+     "vit attention serves 33..192 and 225..256 tokens in fp16 only", "isnew"),
+    ("vit_encode", dict(desc=dict(dtype=N.DT_MXFP8, dim=256, heads=4, mlp=1024, patch=32, kpad=3072)), UNSUP,
+     "vit attention serves 33..192 and 225..256 tokens in fp16 only", "isnew"),
+    ("vit_encode", dict(desc=dict(dim=1280, heads=20, mlp=5120)), UNSUP, "vit dim > 1024 (the head holds a row in LDS)",
+     "isnew"),
+    ("vit_encode", dict(desc=dict(video_dim=1025)), UNSUP, "video_dim > 1024", "isnew"),
     ("vit_encode", dict(B=0), ARG, "vcap_vit_encode: bad arguments"),
     ("vit_encode", dict(prefix_out=P), ARG, "vcap_vit_encode: prefix desc missing"),
     ("vit_encode", dict(ws_bytes=16), WS, "vcap_vit_encode: workspace too small"),
@@ -204,3 +218,19 @@ def test_every_listed_entry_point_has_rows():
 def test_workspace_queries_are_pinned(name, args, expected):
     got = int(getattr(N.lib(), name)(C.byref(_gpt2()), *args))
     assert got == expected and got % 256 == 0
+
+
+@pytest.mark.parametrize("dtype, fields, served", [
+    (N.DT_F16, dict(patch=8, image=64), True),                 # 65 tokens: the generic kernel, fp16 only
+    (N.DT_F32, dict(patch=8, image=64), False),
+    (N.DT_BF16, dict(patch=8, image=64, kpad=192), False),
+    (N.DT_BF16, dict(image=240), False),                       # 226 tokens
+    (N.DT_F32, dict(patch=8, image=32), True),                 # 17 tokens: a window of every dtype
+    (N.DT_F32, dict(dim=1280, heads=20, mlp=5120), False),
+    (N.DT_F32, dict(video_dim=1025), False),
+    (N.DT_F32, dict(video_dim=1024), True),
+])
+def test_vit_workspace_query_is_zero_exactly_where_the_encode_refuses(dtype, fields, served):
+    desc = _vit(dtype=dtype, **fields)
+    assert (int(N.lib().vcap_vit_workspace_bytes(C.byref(desc), 2, 3)) > 0) == served
+    assert (int(N.lib().vcap_vit_layer_fuses_qkv_attention(C.byref(desc), 0)) >= 0) == served

@@ -1,0 +1,108 @@
+"""ViT encoder shape sweep against the fp64 oracle (tests/encoder_shapes.py; DESIGN.md "Encoder shapes" lists
+the kernel each case reaches): thirteen synthetic encoders the ABI accepts and no golden pins - dim 64 .. 1024,
+2 / 17 / 26 / 50 / 65 / 197 / 226 / 257 tokens, patch 8 / 14 / 16 / 32, depth 1 .. 3, B x T from 1 x 1 to 2 x 4,
+video_dim 100, a 3 x 40 prefix - in fp32, bf16 and fp16 (cases 11 - 13 in fp16 only: the other dtypes refuse
+them up front, test_cpu_encoder_shapes.py / test_cpu_abi_refusals.py).  The q / k weights are scaled so that
+every block's softmax is neither uniform nor one-hot.
+
+Per case and precision, on enc_out and (cases 4 and 7) the prefix:
+  1. everything is finite;
+  2. fp32: max |gpu - fp64| <= 1e-4, the project's encoder bar (the fp32 oracle's own error is <= 2.2e-6);
+  3. bf16 / fp16: max |gpu - fp64| < tol = 3 x max |emulated - fp64| and max |gpu - emulated| <= tol / 3 + 1e-4,
+     where `emulated` is the fp64 forward with the type's rounding exactly where the kernels round - both from
+     the two CPU forwards, never from a GPU run (enc_out: bf16 1.3e-2 at dim 64 .. 4.5e-2 at dim 768, fp16
+     2.2e-3 .. 5.9e-3; test_cpu_encoder_shapes.py prints every case's, and shows that the fp16 bound on
+     |gpu - emulated| is not decided by one output ulp: encoder_shapes.fp16_tie_margin);
+  4. row alone: encode(video[b:b+1]) of the last b is bit-identical to row b of the batch (README: a row sums
+     the same way whichever batch it is in);
+  5. GEMM policy: the run forced to the 128x128 kernel and the run with the 256x256 kernel wherever it applies
+     give bf16 / fp16 outputs bit-identical to the automatic one; fp32 stays within the bound of 2 in each;
+  6. workspace_bytes(B, T) > 0, and fuses_qkv_attention(l) is what DESIGN.md says: true in bf16 / fp16 at
+     197 / 257 tokens, false in fp32, at <= 32 tokens and for cases 11 - 13.
+What this net cannot see in bf16 / fp16 (a padding key in the softmax, an unwritten last row tile, at some
+shapes the last key dropped) is measured in test_cpu_encoder_shapes.py and covered by
+test_gpu_attention_edges.py.
+
+Assertion 5 first failed at case 3 in bf16 (then at cases 4 - 10 in bf16 and 3, 7 - 10 in fp16): with the
+256x256 kernel forced, the CLS tail's attn-proj / fc2 lost their K split (that kernel never splits), an unsplit
+sum is another f32 summation order, and the encode differed in the last f32 bits (2.4e-7 .. 4.8e-7; fp16: whole
+output ulps, 2.4e-4 .. 9.8e-4).  vcap_gemm_dispatch now asks the split plan first (csrc/gemm.hip gemm_splits): a
+launch that splits keeps the 128x128 kernel under every policy and tile count.
+
+The sweep is the first run of the N <= 32 attention kernels (vcap_vit_attention_bf16_kernel<2, 2, 4> with and
+without cls_only, vcap_vit_attention_kernel<float, 2>: case 2), of the scalar LayerNorm and the nv = 2 vector
+path inside an encode (cases 1, 3, 5 - 7; 8), of bf16 K = 64 / 192 / 320 GEMMs (cases 1 - 3, 5, 6), of a depth-1
+encoder (5) and of BT = 1 (3)."""
+import pytest
+import torch
+
+import encoder_shapes as S
+from vcap import _native as N
+from vcap.model import HipPrefix, HipViTEncoder
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def gemm_policy():
+    """-> set(p); the automatic policy is restored whatever the test does (as tests/test_gpu_ops.py)."""
+    def set_policy(p):
+        N.check(N.lib().vcap_set_gemm_policy(p), "policy")
+    yield set_policy
+    N.check(N.lib().vcap_set_gemm_policy(0), "policy")
+
+
+def _encode(enc, pre, video):
+    out = enc.encode(video, pre)
+    torch.cuda.synchronize()
+    return [(nm, t.double().cpu()) for nm, t in S.outputs(out)]
+
+
+def _check_against_cpu(cid, prec, got, tag):
+    """Assertions 1 - 3 of the module docstring for one run."""
+    ref = S.outputs(S.reference(cid))
+    assert [nm for nm, _ in got] == [nm for nm, _ in ref], tag
+    for i, ((nm, g), (_, r)) in enumerate(zip(got, ref)):
+        assert g.shape == r.shape and bool(torch.isfinite(g).all()), (tag, nm)
+        e64 = S._maxdiff(g, r)
+        if prec == "fp32":
+            print(f"\nencoder-gpu {tag} {nm}: max|gpu-fp64|={e64:.3e} (bar {S.FP32_TOL:.0e})", end="")
+            assert e64 <= S.FP32_TOL, (tag, nm, e64)
+        else:
+            tol = S.tolerance(cid, prec)[i]
+            eemu = S._maxdiff(g, S.emulated(cid, prec)[i])
+            print(f"\nencoder-gpu {tag} {nm}: max|gpu-fp64|={e64:.3e} (tol {tol:.3e}) "
+                  f"max|gpu-emulated|={eemu:.3e} (bound {tol / 3 + 1e-4:.3e})", end="")
+            assert e64 < tol, (tag, nm, e64, tol)
+            assert eemu <= tol / 3 + 1e-4, (tag, nm, eemu, tol / 3 + 1e-4)
+
+
+@pytest.mark.parametrize("run", S.RUNS, ids=S.run_id)
+def test_encoder_shape_sweep(device, gemm_policy, run):
+    cid, prec = run
+    c = S.BY_ID[cid]
+    sd = S.state_dict(cid)
+    enc = HipViTEncoder(sd, c.arch, prec, device, video_dim=c.video_dim)
+    pre = HipPrefix(sd, c.prefix[1], prefix_len=c.prefix[0], ln_scale=S.LN_SCALE, in_weight=S.IN_WEIGHT,
+                    device=device) if c.prefix else None
+    assert enc.workspace_bytes(c.B, c.T) > 0
+    for layer in range(c.depth):
+        assert enc.fuses_qkv_attention(layer) == S.expect_fused(c, prec), (S.run_id(run), layer)
+    video = S.video(cid).to(device)
+    tag = S.run_id(run)
+    base = _encode(enc, pre, video)
+    _check_against_cpu(cid, prec, base, tag)
+    # 4. the last row encoded alone
+    b = c.B - 1
+    alone = _encode(enc, pre, video[b:b + 1].contiguous())
+    for (nm, a), (_, g) in zip(alone, base):
+        assert torch.equal(a[0], g[b]), (tag, nm, "row alone", S._maxdiff(a[0], g[b]))
+    # 5. the two forced GEMM policies
+    for pol in (1, 2):
+        gemm_policy(pol)
+        got = _encode(enc, pre, video)
+        if prec == "fp32":
+            _check_against_cpu(cid, prec, got, f"{tag} policy{pol}")
+        else:
+            for (nm, a), (_, g) in zip(got, base):
+                assert torch.equal(a, g), (tag, nm, f"policy {pol}", S._maxdiff(a, g))

@@ -171,35 +171,43 @@ __global__ __launch_bounds__(256) void vcap_splitk_reduce_kernel(const float* __
 static thread_local int g_last_splits = 1;
 int vcap_gemm_last_splits() { return g_last_splits; }
 
+// K splits of the 128x128 kernel for one launch (1 = unsplit).
+// Few tiles (the CLS-only last block: M = B*T rows) leave most CUs idle through a long K
+// loop: split K over several workgroups per tile when C is f32 and already holds the
+// residual (attn-proj / fc2 in place) and the caller gave a partials workspace (bf16 / f16 operands
+// only: the fp32 parity mode keeps one summation chain).  The split count depends on K alone
+// (the largest divisor c <= 8 of the K-tile count leaving >= 3 K-tiles per workgroup), never on
+// M or the stream's CU mask, so a row sums the same way whichever batch it is encoded in and a
+// CU-masked pipelined encode sums exactly like a serial one.  (No CU-count gate: a large encode
+// batch takes more rounds of split workgroups instead of switching the summation order.  The
+// encoder's partials workspace holds 16 splits of its B*T CLS rows, so the size check below
+// only refuses a caller-supplied workspace that is too small.)
+// vcap_gemm_dispatch asks the same function: a launch that splits keeps this kernel under every
+// GEMM policy and tile count, because the 256x256 kernel never splits and an unsplit sum is
+// another f32 summation order (tests/test_gpu_encoder_shapes.py found the forced 256x256 policy
+// changing the last bits of an encode through the CLS tail).
+static int gemm_splits(size_t in_size, size_t out_size, const void* C, long ldc, int M, int N, int K,
+                       const GemmEpi& epi) {
+  if (in_size != 2 || out_size != 4) return 1;
+  // launch_gemm gives these launches EPI 2 (plain rows) or EPI 3 (remapped rows), both of which store partials
+  const bool in_place = epi.bias != nullptr && epi.res == (const float*)C && epi.ldr == ldc && epi.res_mode == 1 &&
+                        epi.act == 0 && epi.splitk_ws && (N & 3) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0;
+  if (!in_place) return 1;
+  const int nkt = K / (ROWB / 2);
+  int c = 1;
+  for (int d = 8; d >= 2; --d)
+    if (nkt % d == 0 && nkt / d >= 3) {
+      c = d;
+      break;
+    }
+  return c > 1 && (size_t)c * M * N * sizeof(float) <= epi.splitk_bytes ? c : 1;
+}
+
 template <typename TIn, typename TOut, int EPI>
 static hipError_t launch_gemm_epi(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N,
                                   int K, const GemmEpi& epi, hipStream_t s) {
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  // Few tiles (the CLS-only last block: M = B*T rows) leave most CUs idle through a long K
-  // loop: split K over several workgroups per tile when C is f32 and already holds the
-  // residual (attn-proj / fc2 in place) and the caller gave a partials workspace (bf16 / f16 operands
-  // only: the fp32 parity mode keeps one summation chain).  The split count depends on K alone
-  // (the largest divisor c <= 8 of the K-tile count leaving >= 3 K-tiles per workgroup), never on
-  // M or the stream's CU mask, so a row sums the same way whichever batch it is encoded in and a
-  // CU-masked pipelined encode sums exactly like a serial one.  (No CU-count gate: a large encode
-  // batch takes more rounds of split workgroups instead of switching the summation order.  The
-  // encoder's partials workspace holds 16 splits of its B*T CLS rows, so the size check below
-  // only refuses a caller-supplied workspace that is too small.)
-  int splits = 1;
-  if constexpr (sizeof(TIn) == 2 && sizeof(TOut) == 4) {
-    const bool in_place = epi.bias != nullptr && epi.res == (const float*)C && epi.ldr == ldc &&
-                          (EPI == 2 || (EPI == 3 && epi.res_mode == 1 && epi.act == 0)) && epi.splitk_ws &&
-                          (N & 3) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0;
-    const int nkt = K / (ROWB / (int)sizeof(TIn));
-    int c = 1;
-    for (int d = 8; d >= 2; --d)
-      if (nkt % d == 0 && nkt / d >= 3) {
-        c = d;
-        break;
-      }
-    if (in_place && c > 1 && (size_t)c * M * N * sizeof(float) <= epi.splitk_bytes)
-      splits = c;
-  }
+  const int splits = (EPI == 2 || EPI == 3) ? gemm_splits(sizeof(TIn), sizeof(TOut), C, ldc, M, N, K, epi) : 1;
   g_last_splits = splits;
   hipLaunchKernelGGL((vcap_gemm_kernel<TIn, TOut, EPI>), dim3(tiles, splits), dim3(256), 0, s, (const TIn*)A, lda,
                      (const TIn*)W, ldw, (TOut*)C, ldc, M, N, K, epi);
@@ -274,7 +282,8 @@ hipError_t vcap_gemm_dispatch(int in_dt, int out_dt, const void* A, long lda, co
     if (!vcap_gemm256_ok(in_dt, out_dt, lda, ldw, ldc, M, N, K, epi)) return hipErrorInvalidValue;
     return vcap_gemm256_dispatch(in_dt, out_dt, A, lda, W, ldw, C, ldc, M, N, K, epi, s);
   }
-  if (g_gemm_policy != 1 && vcap_gemm256_ok(in_dt, out_dt, lda, ldw, ldc, M, N, K, epi)) {
+  const bool splits = gemm_splits(vcap_dt_size(in_dt), vcap_dt_size(out_dt), C, ldc, M, N, K, epi) > 1;
+  if (g_gemm_policy != 1 && !splits && vcap_gemm256_ok(in_dt, out_dt, lda, ldw, ldc, M, N, K, epi)) {
     // 256x256 tiles run one workgroup per CU: they need enough tiles to fill the chip, and a
     // last round that is mostly empty costs a whole tile time.  Rows of the full rounds go to
     // the 256x256 kernel, a small remainder to the 128x128 kernel (2 per CU, one short round).

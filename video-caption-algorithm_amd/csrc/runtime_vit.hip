@@ -62,6 +62,12 @@ int check_vit(const vcap_vit_desc* d) {
   if (d->image % d->patch) return fail(VCAP_E_ARG, "image not divisible by patch");
   const int tokens = (d->image / d->patch) * (d->image / d->patch) + 1;
   if (tokens > 288) return fail(VCAP_E_UNSUPPORTED, "more than 288 tokens");
+  // what the encode would otherwise meet after its first launches: a token count the attention dispatcher
+  // has no kernel for in this dtype, and rows the head / prefix kernels cannot hold
+  if (!vcap_vit_attention_supported(vit_adt(d->dtype), tokens))
+    return fail(VCAP_E_UNSUPPORTED, "vit attention serves 33..192 and 225..256 tokens in fp16 only");
+  if (!vcap_vit_head_prefix_supported(d->dim, 1)) return fail(VCAP_E_UNSUPPORTED, "vit dim > 1024 (the head holds a row in LDS)");
+  if (!vcap_vit_head_prefix_supported(1, d->video_dim)) return fail(VCAP_E_UNSUPPORTED, "video_dim > 1024");
   return 0;
 }
 
@@ -132,7 +138,7 @@ int vcap_vit_pool_temporal(int dtype, const void* feat, void* out, int bsz, int 
 int vcap_prefix_project(const float* emb, int B, int video_dim, const vcap_prefix_desc* pd, float* prefix_out,
                         void* stream) {
   if (!emb || !pd || !prefix_out || !pd->mapper_w || B <= 0) return fail(VCAP_E_ARG, "vcap_prefix_project: bad arguments");
-  if (video_dim > 1024) return fail(VCAP_E_UNSUPPORTED, "video_dim > 1024");
+  if (!vcap_vit_head_prefix_supported(1, video_dim)) return fail(VCAP_E_UNSUPPORTED, "video_dim > 1024");
   VCAP_TRY(vcap_vit_head_prefix_dispatch(nullptr, B, 1, 1, 1, nullptr, nullptr, 0.f, nullptr, nullptr, video_dim,
                                          pd->ln_scale, pd->in_weight, pd->mapper_w, pd->mapper_b,
                                          pd->prefix_len * pd->n_embd, nullptr, prefix_out, emb, nullptr,

@@ -128,6 +128,8 @@ hipError_t vcap_mx_quantize_dispatch(int in_dt, const void* x, long ldx, int row
                                      uint8_t* scales, int srows, hipStream_t s);
 hipError_t vcap_layernorm_dispatch(int out_dt, const float* x, long ldx, void* y, long ldy, const float* gamma,
                                    const float* beta, int rows, int D, float eps, hipStream_t s);
+// whether vcap_vit_attention_dispatch has a kernel for N tokens of element type dt (the MXFP8-output form: dt = bf16)
+bool vcap_vit_attention_supported(int dt, int N);
 // cls_only: only the class-token query of each (frame, head), written to compact row `frame`
 hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int BT, int N, int H, hipStream_t s,
                                        int cls_only = 0);
@@ -140,6 +142,7 @@ hipError_t vcap_vit_attention_mx_dispatch(const void* qkv, void* out, uint8_t* o
                                           hipStream_t s, int cls_only = 0);
 hipError_t vcap_patchify_dispatch(int dt, const float* frames, void* patches, float* x, const float* cls,
                                   const float* pos, int BT, int img, int p, int Kp, int N, int D, hipStream_t s);
+bool vcap_vit_head_prefix_supported(int D, int VD);
 hipError_t vcap_vit_head_prefix_dispatch(const float* x, int B, int T, int N, int D, const float* ng, const float* nb,
                                          float neps, const float* pw, const float* pb, int VD, float ln_scale,
                                          float in_weight, const float* mw, const float* mb, int MO, float* enc_out,

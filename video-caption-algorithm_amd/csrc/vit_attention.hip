@@ -916,9 +916,19 @@ static hipError_t attn_generic_dispatch(int kt, const void* qkv, void* out, int 
 //   f32    vcap_vit_attention_kernel<float, kt>                  invalid
 // KE = kt - 1 when the last key tile is all padding (N <= 208, N <= 272), else kt; the f16 generic kernel
 // pads the keys to 64 / 128 / 192 / 256 and masks.  Any other dtype, N <= 0 and N > 288 are invalid.
+// The table above as a predicate: the descriptor check of the encoder (csrc/runtime_vit.hip check_vit)
+// asks it before the first launch, and the dispatcher below asks it again.
+bool vcap_vit_attention_supported(int dt, int N) {
+  if (N <= 0 || N > 288) return false;
+  const int kt = ((N + 31) / 32) * 2;
+  const bool window = kt == 2 || kt == 14 || kt == 18;
+  if (dt == VCAP_DT_F16) return true;  // a window, or the generic kernel (kt <= 16)
+  return (dt == VCAP_DT_BF16 || dt == VCAP_DT_F32) && window;
+}
+
 hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int BT, int N, int H, hipStream_t s,
                                        int cls_only) {
-  if (N <= 0 || N > 288) return hipErrorInvalidValue;
+  if (!vcap_vit_attention_supported(dt, N)) return hipErrorInvalidValue;
   const int kt = ((N + 31) / 32) * 2;
   const bool window = kt == 2 || kt == 14 || kt == 18;
   if (dt == VCAP_DT_BF16) return attn_bf16_dispatch<false, bf16_t>(qkv, out, nullptr, BT, N, H, cls_only, s);
@@ -931,6 +941,6 @@ hipError_t vcap_vit_attention_dispatch(int dt, const void* qkv, void* out, int B
 // bf16 q/k/v -> MXFP8 attention output (+ scales) for the MXFP8 attn-proj GEMM
 hipError_t vcap_vit_attention_mx_dispatch(const void* qkv, void* out, uint8_t* oscale, int BT, int N, int H,
                                           hipStream_t s, int cls_only) {
-  if (N <= 0 || N > 288 || !oscale) return hipErrorInvalidValue;
+  if (!vcap_vit_attention_supported(VCAP_DT_BF16, N) || !oscale) return hipErrorInvalidValue;
   return attn_bf16_dispatch<true, bf16_t>(qkv, out, oscale, BT, N, H, cls_only, s);
 }

@@ -257,6 +257,9 @@ __global__ __launch_bounds__(256) void vcap_prefix_map_kernel(const float* __res
   }
 }
 
+// both kernels hold a row (D pooled features, VD embedding features) in 1024 floats of LDS
+bool vcap_vit_head_prefix_supported(int D, int VD) { return D <= 1024 && VD <= 1024; }
+
 // x == nullptr: prefix only, from emb_in (vcap_prefix_project).  Otherwise the head writes emb
 // to enc_out (or emb_scratch when the caller does not want the encoder output) and the prefix
 // launch reads it from there.
@@ -265,7 +268,7 @@ hipError_t vcap_vit_head_prefix_dispatch(const float* x, int B, int T, int N, in
                                          float in_weight, const float* mw, const float* mb, int MO, float* enc_out,
                                          float* prefix, const float* emb_in, float* emb_scratch, hipStream_t s,
                                          int f16_head) {
-  if (D > 1024 || VD > 1024 || B <= 0) return hipErrorInvalidValue;
+  if (!vcap_vit_head_prefix_supported(D, VD) || B <= 0) return hipErrorInvalidValue;
   const float* emb = emb_in;
   if (x) {
     float* e = enc_out ? enc_out : emb_scratch;
