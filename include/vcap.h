@@ -234,14 +234,30 @@ int vcap_jpeg_decode_batch(const uint8_t* const* data, const size_t* lens, int n
 
 /* ---- MXFP8 (BASELINE configs[4]: fp8 MFMA path for the ViT GEMMs) ----
  * vcap_mx_quantize: rows of f32 / bf16 [rows, K] (row stride ldx) -> e4m3 [rows, K] + scales.
- * vcap_layernorm_mx: LayerNorm (f32 rows) fused with the quantisation of its output.
+ *   Per block of 32: scale byte max(exponent field of max|x| - 7, 0), i.e. 2^(floor(log2 max|x|) - 7)
+ *   clamped at 2^-127 (a block max below 2^-120, f32 subnormals and an all-zero block give byte 0);
+ *   elements x * 2^(127 - scale) rounded to nearest even, |scaled| <= 256, so nothing saturates; -0.0
+ *   stays -0.0 (0x80).  Writes rows * K bytes of q and the scale bytes of rows 0..rows-1 only (the
+ *   padding rows of the last 256-row group are left as they were).
+ *   Non-finite input (tests/test_gpu_mx_sweep.py): other blocks are unaffected.  A NaN takes no part in
+ *   its block's max (fmaxf), so the block's scale and its finite elements are those of the block without
+ *   it, and the NaN is stored as an e4m3 NaN (0x7F / 0xFF).  A block holding +-inf gets scale byte 248:
+ *   its finite elements are scaled by 2^-121 (FLT_MAX -> 128; every |x| below 2^111 has a scaled value
+ *   below 2^-10, half the smallest e4m3 subnormal, and becomes +-0) and the
+ *   infinity itself is stored as whatever the hardware converter gives an overflow - an e4m3 NaN or
+ *   +-448 - the same byte on every run; callers must not rely on which.
+ * vcap_layernorm_mx: LayerNorm (f32 rows) fused with the quantisation of its output (same rule).
  * vcap_gemm_mx: C = epi(A . W^T) with A [M, K], W [N, K] MXFP8 (contiguous rows, K % 256 == 0);
- *   out_dtype BF16 / F32 (res != NULL: C += ..., in place, f32) or MXFP8 (act must be 1 = bias +
+ *   out_dtype BF16 / F32 (res != NULL, f32 only: C = res + ..., res read with C's row stride ldc; res == C
+ *   is the in-place residual add) or MXFP8 (act must be 1 = bias +
  *   GELU-tanh, C e4m3 [M, N] + c_scales (8-byte aligned, vcap_mx_scale_bytes(M, N) bytes: the
- *   padding rows of the last 256-row group are written too), N % 128 == 0). */
+ *   padding rows of the last 256-row group are written too), N % 128 == 0).  N and ldc are multiples
+ *   of 16; rows >= M and columns [N, ldc) of C are never written. */
 size_t vcap_mx_scale_bytes(int rows, int K);
 /* bf16 qkv [frames*tokens, 3*heads*64] -> attention output in MXFP8 ([frames*tokens, heads*64] e4m3 +
- * scales), the A operand of an MXFP8 attn-proj GEMM */
+ * scales, one per 32 of a head's 64 dims, quantised from the f32 value), the A operand of an MXFP8
+ * attn-proj GEMM.  Serves 1..32, 193..224 and 257..288 tokens and heads*64 % 256 == 0; anything else is
+ * VCAP_E_UNSUPPORTED before any launch. */
 int vcap_vit_attention_mx(const void* qkv, void* out, uint8_t* out_scales, int frames, int tokens, int heads,
                           void* stream);
 int vcap_mx_quantize(int in_dtype, const void* x, int64_t ldx, int rows, int K, void* q, uint8_t* scales,

@@ -511,11 +511,15 @@ def mx_scale_bytes(rows: int, K: int) -> int:
 
 
 def mx_quantize(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """f32 [rows, K] -> (e4m3 bytes [rows, K] uint8, E8M0 scales [rows, K/32] uint8)."""
+    """f32 [rows, K] -> (e4m3 bytes [rows, K] uint8, E8M0 scales [rows, K/32] uint8).
+    Non-finite input follows include/vcap.h: a NaN takes no part in the block max (np.fmax, the kernels'
+    fmaxf) and is stored as an e4m3 NaN; a block holding +-inf has scale byte 248.  The byte of an inf
+    element is the one place this function and the device may differ (here 0x7F / 0xFF, torch's cast; the
+    header leaves it open between that and +-448)."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     rows, K = x.shape
     blk = x.reshape(rows, K // 32, 32)
-    amax = np.abs(blk).max(-1).astype(np.float32)
+    amax = np.fmax.reduce(np.abs(blk), axis=-1).astype(np.float32)
     sb = np.maximum(((amax.view(np.uint32) >> 23) & 0xFF).astype(np.int32) - 7, 0)
     inv = ((254 - sb).astype(np.uint32) << 23).view(np.float32)
     q = torch.from_numpy(blk * inv[..., None]).to(torch.float8_e4m3fn).view(torch.uint8).numpy()

@@ -32,6 +32,8 @@ from encoder_shapes import ROUND, generic_attention
 WINDOW_EDGES = (1, 2, 17, 32, 193, 197, 208, 209, 224, 257, 272, 273, 288)
 FP16_MORE = (33, 64, 65, 128, 129, 192, 225, 256)           # the generic kernel's key paddings, both sides
 TOKENS = {"bf16": WINDOW_EDGES, "fp32": WINDOW_EDGES, "fp16": tuple(sorted(WINDOW_EDGES + FP16_MORE))}
+MX_TOKENS = (2, 17, 32, 197, 208, 209, 224, 257, 272, 273, 288)   # two or three per instance of the MXFP8-out kernel
+MX_HEADS = 4
 FUSED_TOKENS = (193, 197, 208, 257, 272)
 F32_TOL = 1e-5
 TORCH = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}

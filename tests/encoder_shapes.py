@@ -21,7 +21,22 @@ accumulator + bias is rounded to fp16 in the patch-embed GEMM (before pos is add
 H16 head (csrc/vit_misc.hip vcap_vit_head_kernel<true>): the pooled row and encoder.proj's weight are
 rounded on the way in, the embedding on the way out.
 The residual stream, the biases, pos, cls, the final LayerNorm, the temporal mean, and the prefix
-normalisation + mapper stay f32 (unrounded here)."""
+normalisation + mapper stay f32 (unrounded here).
+
+Mode "fp8" (precision="fp8": dtype MXFP8 in the descriptor) takes the subset `mx_gemms` of the block GEMMs that
+run in MXFP8; the others, the patch embedding and the QK^T / PV products are the bf16 encoder's.  MXFP8 rounding
+(mxq below: per 32 consecutive elements one scale 2^(floor(log2 max) - 7), elements to e4m3 nearest-even):
+  * patches, the patch-embed weight, q / k / v and P are bf16 as above;
+  * vcap_layernorm_mx_kernel stores norm1 as MXFP8 when qkv is an MXFP8 GEMM, norm2 when fc1 is (else bf16);
+  * vcap_vit_attention_mx writes the attention output as MXFP8 when attn-proj is an MXFP8 GEMM: per 32 of a
+    head's 64 dims, quantised from the f32 value (sum P v) / rowsum, not from its bf16 rounding;
+  * the fc1 epilogue stores GELU(acc + bias) as MXFP8, from the f32 value, when fc1 and fc2 are both MXFP8; an
+    MXFP8 fc2 after a bf16 fc1 quantises the bf16 activation (vcap_mx_quantize);
+  * the weights of an MXFP8 GEMM are mx_quantize of the f32 weights (not of their bf16 rounding).
+With no GEMM selected the mode is the bf16 emulation exactly (asserted in test_cpu_encoder_shapes.py).  `kflip`
+runs every matrix product with its K axis reversed: a second f32 summation order for the bound on
+|gpu - emulated|.  Fault "fc2_scale" (fp8 only): K-block 0 of the last block's fc2 activation doubled - one
+scale byte off by one."""
 from __future__ import annotations
 
 import math
@@ -41,6 +56,7 @@ P = "encoder.backbone."
 FP32_TOL = 1e-4                       # the project's fp32 encoder bar (tests/test_gpu_parity.py)
 LN_SCALE, IN_WEIGHT = 0.6, 0.4        # the engine's prefix normalisation (HipPrefix defaults)
 PRECS = ("fp32", "bf16", "fp16")
+MX_GEMMS = ("qkv", "proj", "fc1", "fc2")      # HipViTEncoder.MX_GEMMS
 FAULTS = ("drop_key", "pad_key", "row_tile", "pos_late", "fc2_ktile", "frame_missing")
 ASSERTED_16 = ("fc2_ktile", "frame_missing")   # the faults a half-precision end-to-end check must see
 SCORE_STD, MAXP_MEDIAN = (1.0, 4.0), (0.05, 0.9)
@@ -100,6 +116,24 @@ CASES = (
 )
 BY_ID = {c.cid: c for c in CASES}
 RUNS = [(c.cid, p) for c in CASES for p in c.precs]
+# The fp8 sweep: its own cases and run list (the table above and its assertions are untouched).  B * T <= 8.
+FP8_CASES = (
+    Case(21, 256, 4, 16, 16, 2, 2, 3, "fp8: M = 12, a 6-row CLS tail; LN-MX nv = 1", precs=("fp8",), qk=7.5),
+    Case(22, 256, 4, 8, 32, 1, 2, 2, "fp8: the only block is the CLS tail", precs=("fp8",)),
+    Case(23, 256, 4, 16, 224, 2, 1, 2, "fp8: M = 394, two 256-row scale groups; the per-GEMM mixes", precs=("fp8",)),
+    # B = 2 so that the last row encoded alone has fewer 256-row scale groups than the batch: 5 -> 3 at 257 tokens
+    # (M = 1028 -> 514), 4 -> 2 at 197 tokens (788 -> 394).  Case 23 is the issue's 1 x 2: its row alone IS the batch.
+    Case(24, 512, 8, 14, 224, 2, 2, 2, "fp8: case 8's architecture, 257 tokens; LN-MX nv = 2", precs=("fp8",)),
+    Case(25, 768, 12, 16, 224, 2, 2, 2, "fp8: case 10's architecture; LN-MX nv = 3", precs=("fp8",)),
+    Case(26, 1024, 16, 16, 224, 2, 2, 2, "fp8: case 9's architecture; LN-MX nv = 4", precs=("fp8",)),
+)
+BY_ID.update({c.cid: c for c in FP8_CASES})
+FP8_MIXES = (("qkv",), ("proj",), ("fc1",), ("fc2",), ("qkv", "proj"))
+FP8_RUNS = [(c.cid, MX_GEMMS) for c in FP8_CASES] + [(23, m) for m in FP8_MIXES]
+
+
+def fp8_run_id(run) -> str:
+    return f"{BY_ID[run[0]].name}-fp8-{'+'.join(run[1]) if run[1] != MX_GEMMS else 'all'}"
 # (case, precision) pairs the descriptor check refuses (tests/test_cpu_abi_refusals.py pins code and text)
 REFUSED = [(c.cid, p) for c in CASES for p in ("fp32", "bf16") if p not in c.precs]
 
@@ -158,7 +192,17 @@ def _ident(x):
     return x
 
 
+def mxq(x: torch.Tensor) -> torch.Tensor:
+    """MXFP8 quantise-dequantise along the last axis (blocks of 32), in x's dtype: oracle.mx_quantize's rule."""
+    shp = x.shape
+    b = x.reshape(*shp[:-1], shp[-1] // 32, 32)
+    _, e = torch.frexp(b.abs().amax(-1, keepdim=True))           # max = m 2^e, m in [0.5, 1): floor(log2) = e - 1
+    scale = torch.ldexp(torch.ones_like(b[..., :1]), (e - 8).clamp(min=-127))
+    return ((b / scale).to(torch.float32).to(torch.float8_e4m3fn).to(x.dtype) * scale).reshape(shp)
+
+
 ROUND = {"fp64": _ident, "bf16": _rne(torch.bfloat16), "fp16": _rne(torch.float16)}
+_MX_KEY = {"qkv": "attn.qkv.weight", "proj": "attn.proj.weight", "fc1": "mlp.fc1.weight", "fc2": "mlp.fc2.weight"}
 _MATS = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight", "patch_embed.proj.weight")
 
 
@@ -176,6 +220,18 @@ def sd64(cid: int, mode: str = "fp64") -> Dict[str, torch.Tensor]:
     return out
 
 
+@lru_cache(maxsize=None)
+def sd64_fp8(cid: int, mx_gemms: Tuple[str, ...]) -> Dict[str, torch.Tensor]:
+    """sd64(cid, "bf16") with the weights of the MXFP8 GEMMs replaced by mx_quantize of the f32 weights."""
+    out = dict(sd64(cid, "bf16"))
+    raw = state_dict(cid)
+    for i in range(BY_ID[cid].depth):
+        for g in mx_gemms:
+            k = f"{P}blocks.{i}.{_MX_KEY[g]}"
+            out[k] = mxq(torch.from_numpy(np.ascontiguousarray(raw[k])).double())
+    return out
+
+
 def generic_attention(mode: str, tokens: int) -> bool:
     """Whether vcap_vit_attention_dispatch gives this (precision, token count) the generic kernel, whose
     row sum is taken over the unrounded P (module docstring)."""
@@ -184,7 +240,8 @@ def generic_attention(mode: str, tokens: int) -> bool:
 
 
 def forward(cid: int, mode: str = "fp64", fault: Optional[str] = None, stats: Optional[list] = None,
-            frames: Optional[torch.Tensor] = None, arith: torch.dtype = torch.float64, raw: Optional[list] = None):
+            frames: Optional[torch.Tensor] = None, arith: torch.dtype = torch.float64, raw: Optional[list] = None,
+            mx_gemms: Optional[Tuple[str, ...]] = None, kflip: bool = False):
     """-> (enc_out [B, video_dim], prefix [B, P, E] or None), float64.
 
     mode "fp64": no rounding (oracle.encoder + prefix_norm + mapper, asserted on the CPU); "bf16" / "fp16":
@@ -192,10 +249,23 @@ def forward(cid: int, mode: str = "fp64", fault: Optional[str] = None, stats: Op
     block (std of the scaled scores q.k / 8, median over rows of the row's largest probability).
     `frames` [b, T, 3, H, W] replaces the case's video.  `arith` = torch.float32 runs the same forward with f32
     arithmetic between the roundings (what any kernel with f32 accumulators does, in another order).  `raw`, a
-    list, receives encoder.proj's output before the fp16 head rounds it."""
+    list, receives encoder.proj's output before the fp16 head rounds it.  mode "fp8": `mx_gemms` (default all
+    four) run in MXFP8, the rest as bf16; `kflip`: every matrix product sums its K axis in reverse."""
     c = BY_ID[cid]
+    mxg = () if mode != "fp8" else MX_GEMMS if mx_gemms is None else tuple(g for g in MX_GEMMS if g in mx_gemms)
+    if mode == "fp8":
+        mode = "bf16"
+        sd0 = sd64_fp8(cid, mxg)
+    else:
+        sd0 = sd64(cid, mode)
     ar, rnd = c.arch, ROUND[mode]
-    sd = sd64(cid, mode) if arith == torch.float64 else {k: v.to(arith) for k, v in sd64(cid, mode).items()}
+    sd = sd0 if arith == torch.float64 else {k: v.to(arith) for k, v in sd0.items()}
+
+    def mm(a, w):                                # a @ w^T
+        return a.flip(-1) @ w.flip(-1).t() if kflip else a @ w.t()
+
+    def rnd_for(gemm):                           # the rounding of the A operand of a block GEMM
+        return mxq if gemm in mxg else rnd
     lin = rnd if mode == "fp16" else _ident      # Autocast<f16_t>: a Linear's accumulator + bias is fp16
     d, heads, n, npatch = ar.dim, ar.heads, ar.tokens, ar.num_patches
     vid = (video(cid) if frames is None else frames).to(arith)
@@ -209,43 +279,48 @@ def forward(cid: int, mode: str = "fp64", fault: Optional[str] = None, stats: Op
         ppos = pos[1:]
         if fault == "pos_late" and npatch > 1:
             ppos = torch.roll(ppos, -1, 0)       # patch p takes the row of patch p + 1
-        x = lin(patches @ pw.t() + sd[P + "patch_embed.proj.bias"]) + ppos
+        x = lin(mm(patches, pw) + sd[P + "patch_embed.proj.bias"]) + ppos
         cls = (sd[P + "cls_token"].reshape(d) + pos[0]).expand(bt, 1, d)
         x = torch.cat([cls, x], dim=1)
         for i in range(ar.depth):
             b = f"{P}blocks.{i}."
             last = i == ar.depth - 1
-            h = rnd(F.layer_norm(x, (d,), sd[b + "norm1.weight"], sd[b + "norm1.bias"], ar.ln_eps))
-            qkv = rnd(h @ sd[b + "attn.qkv.weight"].t() + sd[b + "attn.qkv.bias"])
+            h = rnd_for("qkv")(F.layer_norm(x, (d,), sd[b + "norm1.weight"], sd[b + "norm1.bias"], ar.ln_eps))
+            qkv = rnd(mm(h, sd[b + "attn.qkv.weight"]) + sd[b + "attn.qkv.bias"])
             q, k, v = qkv.reshape(bt, n, 3, heads, 64).permute(2, 0, 3, 1, 4).unbind(0)
             if fault == "drop_key" and n > 1:
                 k, v = k[:, :, :-1], v[:, :, :-1]
             if fault == "pad_key":
                 z = torch.zeros(bt, heads, 1, 64, dtype=arith)
                 k, v = torch.cat([k, z], 2), torch.cat([v, z], 2)
-            s = q @ k.transpose(-1, -2) / 8.0
+            s = (q.flip(-1) @ k.flip(-1).transpose(-1, -2) if kflip else q @ k.transpose(-1, -2)) / 8.0
             e = torch.exp(s - s.max(-1, keepdim=True).values)
             if stats is not None:
                 stats.append((float(s.std()), float((e / e.sum(-1, keepdim=True)).max(-1).values.median())))
             pr = rnd(e)
             den = (e if generic_attention(mode, n) else pr).sum(-1, keepdim=True)
-            a = rnd((pr @ v) / den).transpose(1, 2).reshape(bt, n, d)
-            upd = lin(a @ sd[b + "attn.proj.weight"].t() + sd[b + "attn.proj.bias"])
+            a = rnd_for("proj")((pr.flip(-1) @ v.flip(-2) if kflip else pr @ v) / den).transpose(1, 2).reshape(bt, n, d)
+            upd = lin(mm(a, sd[b + "attn.proj.weight"]) + sd[b + "attn.proj.bias"])
             if fault == "row_tile" and i == 0 and not last:
                 upd = upd.clone()
                 upd[:, n - (n % 16 or 16):] = 0.0   # the residual rows keep what they held
             x = x + upd
-            h = rnd(F.layer_norm(x, (d,), sd[b + "norm2.weight"], sd[b + "norm2.bias"], ar.ln_eps))
-            h = rnd(F.gelu(lin(h @ sd[b + "mlp.fc1.weight"].t() + sd[b + "mlp.fc1.bias"]), approximate="tanh"))
+            h = rnd_for("fc1")(F.layer_norm(x, (d,), sd[b + "norm2.weight"], sd[b + "norm2.bias"], ar.ln_eps))
+            h = F.gelu(lin(mm(h, sd[b + "mlp.fc1.weight"]) + sd[b + "mlp.fc1.bias"]), approximate="tanh")
+            # MXFP8 fc2: from the f32 value when fc1 is MXFP8 too (its epilogue), else from the bf16 activation
+            h = mxq(h) if "fc1" in mxg and "fc2" in mxg else mxq(rnd(h)) if "fc2" in mxg else rnd(h)
             if fault == "fc2_ktile" and last:
                 h = h.clone()
                 h[..., -64:] = 0.0
-            x = x + lin(h @ sd[b + "mlp.fc2.weight"].t() + sd[b + "mlp.fc2.bias"])
+            if fault == "fc2_scale" and last:
+                h = h.clone()
+                h[..., :32] *= 2.0
+            x = x + lin(mm(h, sd[b + "mlp.fc2.weight"]) + sd[b + "mlp.fc2.bias"])
         feat = F.layer_norm(x[:, 0], (d,), sd[P + "norm.weight"], sd[P + "norm.bias"], ar.ln_eps).reshape(bsz, t, d)
         pooled = (feat[:, :-1] if fault == "frame_missing" else feat).sum(1) / t
         if mode == "fp16":
             pooled = rnd(pooled)
-        emb = pooled @ sd["encoder.proj.weight"].t() + sd["encoder.proj.bias"]
+        emb = mm(pooled, sd["encoder.proj.weight"]) + sd["encoder.proj.bias"]
         if raw is not None:
             raw.append(emb.double())
         emb = lin(emb)
@@ -280,6 +355,21 @@ def reference(cid: int):
 @lru_cache(maxsize=None)
 def emulated(cid: int, mode: str):
     return forward(cid, mode)
+
+
+@lru_cache(maxsize=None)
+def emulated_fp8(cid: int, mx_gemms: Tuple[str, ...]):
+    return forward(cid, "fp8", mx_gemms=mx_gemms)
+
+
+def tolerance_fp8(cid: int, mx_gemms: Tuple[str, ...]) -> float:
+    """3 x max |emulated - fp64| on enc_out of an fp8 run, as tolerance() below: from two CPU forwards alone."""
+    return 3.0 * _maxdiff(emulated_fp8(cid, mx_gemms)[0], reference(cid)[0])
+
+
+def expect_fused_fp8(c: Case, mx_gemms: Tuple[str, ...]) -> bool:
+    """fp8: the fused QKV + attention kernel runs where bf16's does unless qkv or attn-proj is an MXFP8 GEMM."""
+    return expect_fused(c, "bf16") and "qkv" not in mx_gemms and "proj" not in mx_gemms
 
 
 def _maxdiff(a, b) -> float:

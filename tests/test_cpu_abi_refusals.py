@@ -9,7 +9,10 @@ vcap_gpt2_beam_search with no context row (they used to launch on zero rows) and
 a prompt id outside the vocabulary (it used to embed it).  Greedy and sampling decode have no row for a
 context above 1024: with at most 512 prefill rows and 64 new tokens no call reaches it.  The "isnew" rows of
 vcap_vit_encode came with the encoder shape sweep (tests/encoder_shapes.py): shapes check_vit used to accept and
-the encode then failed on after its first launches (-hipErrorInvalidValue from "attention" / "head_prefix")."""
+the encode then failed on after its first launches (-hipErrorInvalidValue from "attention" / "head_prefix").  Those of
+vcap_vit_attention_mx came with the MXFP8 kernel sweep (tests/test_gpu_mx_sweep.py): 33..192 and 225..256 tokens
+used to come back from the dispatcher as -hipErrorInvalidValue ("invalid argument"), not as a documented code; the
+entry point now asks vcap_vit_attention_supported before the dispatcher."""
 import ctypes as C
 
 import pytest
@@ -78,9 +81,10 @@ GOOD = {
                              stream=None),
     "vit_encode": dict(d=_vit, pd=None, frames=P, B=1, T=2, enc=P, prefix_out=None, ws=P, ws_bytes=BIG, stream=None),
     "vit_layer_fuses": dict(d=_vit, layer=0),
+    "vit_attention_mx": dict(qkv=P, out=P, scales=P, frames=2, tokens=197, heads=4, stream=None),
 }
 SYMBOL = {"decode_attention": "vcap_decode_attention", "vit_encode": "vcap_vit_encode",
-          "vit_layer_fuses": "vcap_vit_layer_fuses_qkv_attention"}
+          "vit_layer_fuses": "vcap_vit_layer_fuses_qkv_attention", "vit_attention_mx": "vcap_vit_attention_mx"}
 
 # (entry point, the argument made bad, code, message, new?)   desc=/gp=/bp=/sp= give descriptor fields
 ROWS = [
@@ -167,6 +171,11 @@ ROWS = [
     ("vit_encode", dict(prefix_out=P), ARG, "vcap_vit_encode: prefix desc missing"),
     ("vit_encode", dict(ws_bytes=16), WS, "vcap_vit_encode: workspace too small"),
     ("vit_layer_fuses", dict(layer=2), ARG, "vcap_vit_layer_fuses_qkv_attention: layer out of range"),
+    ("vit_attention_mx", dict(frames=0), ARG, "vcap_vit_attention_mx: bad arguments"),
+    ("vit_attention_mx", dict(tokens=289), UNSUP, "vcap_vit_attention_mx: tokens > 288"),
+    ("vit_attention_mx", dict(heads=3), UNSUP, "vcap_vit_attention_mx: heads*64 must be a multiple of 256"),
+    ("vit_attention_mx", dict(tokens=33), UNSUP, "vcap_vit_attention_mx: serves 1..32, 193..224 and 257..288 tokens", "isnew"),
+    ("vit_attention_mx", dict(tokens=225), UNSUP, "vcap_vit_attention_mx: serves 1..32, 193..224 and 257..288 tokens", "isnew"),
 ]
 
 

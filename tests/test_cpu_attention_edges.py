@@ -7,14 +7,21 @@ are far outside the tolerance here.  pytest -s prints the tolerance per pattern.
   * pattern 1 gives v_j to within exp(-16) N max |v|, pattern 2 the mean of v;
   * the fused kernel's xn / W reproduce the same q / k exactly;
   * the last key dropped (pattern 1 with j = N - 1) and a padding key admitted (pattern 2) move the output by
-    more than 100 x the tolerance; the output shifted by one row moves pattern 3 by more than the tolerance."""
+    more than 100 x the tolerance; the output shifted by one row moves pattern 3 by more than the tolerance;
+  * MXFP8 output (heads = 4): the same three faults, and a row tile left unwritten, each push at least one
+    element past the per-element MXFP8 bound (half an e4m3 step of its block + the bf16 tolerance) at every
+    token count of the MXFP8 runs, and the bf16 emulation itself stays inside that bound."""
 import math
+
+import numpy as np
 
 import pytest
 import torch
 
 import attention_edge_cases as A
+import mx_cases as MX
 from encoder_shapes import generic_attention
+from oracle import vcap_oracle as O
 
 RUNS = [(p, n) for p in ("bf16", "fp16", "fp32") for n in A.TOKENS[p]]
 
@@ -85,3 +92,35 @@ def test_fused_inputs_give_the_same_q_and_k(prec, n):
         assert torch.equal(got[:, :, :2], qk)
         assert torch.equal(qk, A.qkv(pattern, prec, n, j=j)[:, :, :2])
         assert 0.2 < float(got[:, :, 2].std()) < 2.0                             # a random v of ordinary size
+
+
+@pytest.mark.parametrize("n", A.MX_TOKENS)
+def test_faults_exceed_the_mxfp8_bound(n):
+    frames, heads = 2, A.MX_HEADS
+    M, D = frames * n, heads * 64
+    assert A.MX_TOKENS == MX.ATTN_TOKENS and (heads * 64) % 256 == 0
+
+    def over(x, moved, ref, term):
+        return bool((np.abs(moved.reshape(M, D).numpy() - ref.reshape(M, D).numpy()) > MX.attention_mx_bound(ref.reshape(M, D).numpy(), term)).any())
+
+    seen = set()
+    for pattern, j in A.variants(n):
+        x = A.qkv(pattern, "bf16", n, frames, heads, j)
+        ref = A.attend(x)
+        term = A.tolerance(x, "bf16", ref)
+        # the emulated kernel output, quantised, passes its own check
+        q, s = O.mx_quantize(A.attend(x, "bf16").reshape(M, D).float().numpy())
+        assert not MX.attention_mx_check(ref.reshape(M, D).numpy(), term, q, s), (pattern, j)
+        if pattern == "dominant" and j == n - 1:
+            assert over(x, A.attend(x, fault="drop_key"), ref, term)
+            seen.add("drop_key")
+        if pattern == "uniform":
+            assert over(x, A.attend(x, fault="pad_key"), ref, term)
+            seen.add("pad_key")
+        if pattern == "permutation":
+            assert over(x, torch.roll(ref, 1, dims=1), ref, term)
+            tile = ref.clone()
+            tile[:, n - (n % 16 or 16):] = 0.0            # the last row tile never stored (a zeroed buffer)
+            assert over(x, tile, ref, term)
+            seen.add("row_tile")
+    assert seen == {"drop_key", "pad_key", "row_tile"}

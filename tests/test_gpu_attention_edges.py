@@ -15,12 +15,19 @@ types 3 x max |emulated - fp64| per input, from the CPU alone (about 3e-4 / 1.4e
 in bf16 at 197 tokens).  The fused kernel must also equal the unfused pair bit for bit, and its cls_only form the
 class-token rows of the full run, with nothing written past the compact rows.
 
+  mxfp8         vcap_vit_attention_mx (bf16 in, MXFP8 out) at heads = 4: 2, 17, 32 (<2,2,4>) | 197, 208 (<14,13,8>) |
+                209, 224 (<14,14,8>) | 257, 272 (<18,17,8>) | 273, 288 (<18,18,8>); the bound is half an e4m3 step
+                of the element's block + the bf16 tolerance, the scales within the window that tolerance leaves
+                around a power of two (tests/mx_cases.py attention_mx_check)
+
 These are the first runs of vcap_vit_attention_bf16_kernel<2, 2, 4> and vcap_vit_attention_kernel<float, 2>
 outside an encode (tests/test_gpu_encoder_shapes.py case 2 runs them inside one)."""
 import pytest
 import torch
 
 import attention_edge_cases as A
+import mx_cases as MX
+from oracle import vcap_oracle as O
 from vcap import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -86,3 +93,27 @@ def test_fused_attention_edges(device, prec, n, frames):
         want = full.view(frames, n, d)[:, 0].contiguous()
         assert torch.equal(cls[:frames].view(torch.int16), want.view(torch.int16)), tag
         assert bool(torch.isnan(cls[frames:].float()).all()), tag
+
+
+@pytest.mark.parametrize("n", A.MX_TOKENS)
+def test_attention_edges_mxfp8(device, n):
+    """The fourth precision: the three patterns through vcap_vit_attention_mx, 2 frames x 4 heads (197 and 257
+    tokens cross a 256-row scale group).  Nothing is written past the last row or past vcap_mx_scale_bytes."""
+    frames, heads = 2, A.MX_HEADS
+    M, D = frames * n, heads * 64
+    nsc = int(N.lib().vcap_mx_scale_bytes(M, D))
+    for pattern, j in A.variants(n):
+        tag = f"mxfp8 N={n} H={heads} {pattern}{'' if j is None else j}"
+        x = A.qkv(pattern, "bf16", n, frames, heads, j)
+        qkv = x.reshape(M, 3 * D).to(torch.bfloat16).to(device)
+        q = torch.full((M + 1, D), 0xA5, dtype=torch.uint8, device=device)
+        sc = torch.full((nsc + 64,), 0xA5, dtype=torch.uint8, device=device)
+        N.check(N.lib().vcap_vit_attention_mx(qkv.data_ptr(), q.data_ptr(), sc.data_ptr(), frames, n, heads, _s()), "attention_mx")
+        torch.cuda.synchronize()
+        ref = A.attend(x)
+        term = A.tolerance(x, "bf16", ref)
+        qg, sflat = q.cpu().numpy(), sc.cpu().numpy()
+        bad = MX.attention_mx_check(ref.reshape(M, D).numpy(), term, qg[:M], O.mx_unpack_scales(sflat[:nsc], M, D))
+        print(f"\nattention-gpu {tag}: instance {MX.attention_instance(n)}, bf16 term {term:.3e}", end="")
+        assert not bad, (tag, bad)
+        assert (qg[M:] == 0xA5).all() and (sflat[nsc:] == 0xA5).all(), tag

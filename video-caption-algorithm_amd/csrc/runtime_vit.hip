@@ -120,6 +120,8 @@ int vcap_vit_attention_mx(const void* qkv, void* out, uint8_t* out_scales, int f
     return fail(VCAP_E_ARG, "vcap_vit_attention_mx: bad arguments");
   if (tokens > 288) return fail(VCAP_E_UNSUPPORTED, "vcap_vit_attention_mx: tokens > 288");
   if ((heads * 64) % 256) return fail(VCAP_E_UNSUPPORTED, "vcap_vit_attention_mx: heads*64 must be a multiple of 256");
+  if (!vcap_vit_attention_supported(VCAP_DT_BF16, tokens))
+    return fail(VCAP_E_UNSUPPORTED, "vcap_vit_attention_mx: serves 1..32, 193..224 and 257..288 tokens");
   VCAP_TRY(vcap_vit_attention_mx_dispatch(qkv, out, out_scales, frames, tokens, heads, (hipStream_t)stream),
            "vcap_vit_attention_mx");
   return 0;
