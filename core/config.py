@@ -78,3 +78,5 @@ class InferenceConfig:
     tokenizer_dir: str = ""                 # local vocab.json + merges.txt for string prompts
     use_hipgraph: bool = True
     sample_seed: int = 0
+    # candidates that share a preset and do not sample decode in one device call, a prompt per row
+    merge_candidates: bool = True

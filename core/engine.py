@@ -5,11 +5,14 @@ encoder -> proj -> layer_norm(emb) * ln_scale * in_weight -> decoder.generate(pr
 clean_text; infer() runs the three configured candidates and select_best.  The encoder +
 LN-scale + mapper run as one fused HIP call, and infer() encodes the video ONCE for its three
 candidates (the reference re-runs the ViT per candidate, core/engine.py:43; results identical).
+Candidates that share a preset and do not sample are decoded in ONE device call with a prompt per row
+(ragged prompts: each row gives what its own call gives), so the default config - S1 and S2 both
+`precise`, different prompts - runs two decodes, not three (InferenceConfig.merge_candidates).
 """
 from __future__ import annotations
 
 import logging
-from typing import List, Sequence
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
@@ -60,15 +63,52 @@ class InferenceEngine:
                                   device=self.device)
         return self.infer_video(video)
 
+    def _candidate_groups(self) -> List[Tuple[Dict, List[int]]]:
+        """The three candidates as decode calls: [(preset kwargs, candidate indices)].  Candidates with
+        equal preset_to_kwargs that do not sample share one call (a prompt per row).  A sampling
+        candidate always decodes alone: its Philox counter carries the row index, so its draws would
+        change with its place in a merged batch."""
+        c = self.config
+        groups: List[Tuple[Dict, List[int]]] = []
+        for i, preset in enumerate((c.preset1, c.preset2, c.preset3)):
+            kw = preset_to_kwargs(preset)
+            samples = kw.get("num_beams", 3) == 1 and kw.get("temperature", 1.0) != 1.0
+            if c.merge_candidates and not samples:
+                hit = next((g for g in groups if g[0] == kw and not g[2]), None)
+                if hit is not None:
+                    hit[1].append(i)
+                    continue
+            groups.append((kw, [i], samples))
+        return [(kw, idx) for kw, idx, _ in groups]
+
+    def _decode_candidates(self, prefix: torch.Tensor) -> List[List[str]]:
+        """Every candidate's caption for every row of `prefix` [B, P, E]: out[candidate][video].  A group
+        of n candidates decodes B * n rows, row (video, candidate), each video's prefix rows repeated."""
+        c, dec = self.config, self.model.decoder
+        prompts = (c.prompt1, c.prompt2, c.prompt3)
+        B = prefix.shape[0]
+        out: List[List[str]] = [[], [], []]
+        for kw, idx in self._candidate_groups():
+            if len(idx) == 1:
+                out[idx[0]] = self._decode_rows(prefix, prompts[idx[0]], **kw)
+                continue
+            n = len(idx)
+            ids = [dec.tokenizer.encode_prompt(prompts[i] or "") for i in idx]
+            rows = dec.generate_from_prefix(
+                prefix.repeat_interleave(n, dim=0), [ids[k] for _ in range(B) for k in range(n)],
+                max_new_tokens=kw.get("max_new_tokens", 24), num_beams=kw.get("num_beams", 3),
+                temperature=kw.get("temperature", 1.0), top_p=kw.get("top_p", 1.0),
+                no_repeat_ngram_size=kw.get("no_repeat_ngram_size", 3),
+                repetition_penalty=kw.get("repetition_penalty", 1.1), min_new_tokens=8, seed=c.sample_seed)
+            texts = [clean_text(t.strip()) for t in dec.tokenizer.batch_decode(rows, skip_special_tokens=True)]
+            for k, i in enumerate(idx):
+                out[i] = texts[k::n]
+        return out
+
     @torch.no_grad()
     def infer_video(self, video: torch.Tensor) -> InferenceResult:
-        prefix = self._prefix(video)
-        c = self.config
-        cands = CaptionCandidates(
-            s1=self._decode(prefix, c.prompt1, **preset_to_kwargs(c.preset1)),
-            s2=self._decode(prefix, c.prompt2, **preset_to_kwargs(c.preset2)),
-            s3=self._decode(prefix, c.prompt3, **preset_to_kwargs(c.preset3)),
-        )
+        s1, s2, s3 = self._decode_candidates(self._prefix(video)[:1])
+        cands = CaptionCandidates(s1=s1[0], s2=s2[0], s3=s3[0])
         key, text, _ = select_best([("S1", cands.s1), ("S2", cands.s2), ("S3", cands.s3)])
         return InferenceResult(candidates=cands, best_key=key, best_text=text)
 
@@ -89,12 +129,8 @@ class InferenceEngine:
     @torch.no_grad()
     def infer_videos(self, videos: torch.Tensor) -> List[InferenceResult]:
         """infer_video over a batch [B, T, 3, H, W]: ONE fused encode for all B videos and one
-        batched decode per candidate (the serving path coalesces requests into this call)."""
-        prefix = self._prefix(videos)
-        c = self.config
-        s1 = self._decode_rows(prefix, c.prompt1, **preset_to_kwargs(c.preset1))
-        s2 = self._decode_rows(prefix, c.prompt2, **preset_to_kwargs(c.preset2))
-        s3 = self._decode_rows(prefix, c.prompt3, **preset_to_kwargs(c.preset3))
+        batched decode per candidate group (the serving path coalesces requests into this call)."""
+        s1, s2, s3 = self._decode_candidates(self._prefix(videos))
         out = []
         for a, b, d in zip(s1, s2, s3):
             key, text, _ = select_best([("S1", a), ("S2", b), ("S3", d)])

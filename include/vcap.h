@@ -584,6 +584,41 @@ int vcap_text_encode(const vcap_text_desc* d, const int* ids /* device [B][L] */
                      float* hidden_out /* optional device [B][L][dim]: the encoder output before the pool */,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- ragged prompts (added within ABI v16: new symbols and one struct only): one device decode for B
+ *      rows with a prompt each.  The contract is per row: row b's tokens, raw logits, warped scores and
+ *      beam result are those of the uniform entry point (vcap_gpt2_generate / _sample / _beam_search)
+ *      called with B = 1, prefix row b and prompt b.  Output layouts are the uniform calls':
+ *      out_ids [B][max_new], logits_out / warped_out [max_new][B][vocab], force_ids [B][max_new],
+ *      beam out_ids [B][max_new] + out_len [B].  A sampling row b draws from Philox counter (step, b), so
+ *      only row 0's free draw is the B = 1 call's draw; with force_ids every row's warped scores are.
+ *      The prefill packs its rows with no padding, sequence-major: M = sum_b (prefix_len + len_b) rows
+ *      (times num_beams for the search's replicated prefill).  Sequence b occupies positions
+ *      0 .. S0_b - 1 (S0_b = prefix_len + len_b) and its step t runs at position S0_b + t.  The
+ *      processors see generated tokens only.  The prompt ids and the row tables are uploaded to the
+ *      workspace on `stream` before the first launch, outside the captured graph: one graph (keyed by B,
+ *      the offsets, the parameters and the pointers) serves every set of ids with those lengths.
+ *      Limits, each refused before any launch (the workspace queries return 0): every len_b in [0, 64]
+ *      and S0_b > 0; M <= vcap_gpt2_max_rows(); S0_b + max_new <= n_positions; offsets[0] == 0 and
+ *      non-decreasing; ids inside the vocabulary; beam search also B <= 8, 2 <= num_beams <= 8,
+ *      max_new <= 64 and max_b S0_b + max_new <= 128.  VCAP_E_ARG / VCAP_E_UNSUPPORTED as the uniform
+ *      calls give them. ---- */
+typedef struct vcap_prompts {   /* host memory */
+  const int* ids;       /* the B prompts concatenated (may be NULL when every prompt is empty) */
+  const int* offsets;   /* [B + 1], offsets[0] == 0, non-decreasing; prompt b = ids[offsets[b] .. offsets[b+1]) */
+} vcap_prompts;
+size_t vcap_gpt2_ragged_workspace_bytes(const vcap_gpt2_desc* d, const int* offsets, int B, int max_new_tokens);
+int vcap_gpt2_generate_ragged(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const float* prefix,
+                              const vcap_prompts* prompts, int B, int* out_ids, float* logits_out, void* workspace,
+                              size_t ws_bytes, void* stream);
+int vcap_gpt2_sample_ragged(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const vcap_sample_params* sp,
+                            const float* prefix, const vcap_prompts* prompts, int B, int* out_ids, float* logits_out,
+                            float* warped_out, const int* force_ids, void* workspace, size_t ws_bytes, void* stream);
+size_t vcap_gpt2_beam_search_ragged_workspace_bytes(const vcap_gpt2_desc* d, const int* offsets, int B, int num_beams,
+                                                    int max_new_tokens);
+int vcap_gpt2_beam_search_ragged(const vcap_gpt2_desc* d, const vcap_beam_params* bp, const float* prefix,
+                                 const vcap_prompts* prompts, int B, int* out_ids, int* out_len, void* workspace,
+                                 size_t ws_bytes, void* stream);
+
 /* ---- live kernel timing for the benchmark's roofline (sites: "vit.qkv", "vit.attention",
  *      "vit.proj", "vit.fc1", "vit.fc2"): events are recorded around each launch of the site on
  *      the caller's stream, without synchronising; vcap_probe_read waits for them. ---- */

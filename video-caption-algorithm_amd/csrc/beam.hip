@@ -200,9 +200,22 @@ VCAP_DEV int pick(const int (&a)[NB], int idx) {
 // One workgroup, wave b = batch b (B <= 8: 2 waves per SIMD, a 256-register budget).  Restates search.py beam_search (itself token-identical to the
 // reference's HF beam search, tests/test_gpu_search.py) for one step `cur`.  Lane p holds position
 // p (and p + 64 of the ancestry rows) of every beam of its batch; all state is loaded up front.
-template <int NB, int NC>   // NC: candidates per lane (NB * C * K <= 64 * NC)
+// PER_SEQ (ragged prompts): S0 is per batch - s0.of(row) = seq_len[row], asked for row b * NB - instead of one value.
+template <bool PER_SEQ>
+struct BeamS0 {
+  int v;
+  VCAP_DEV int of(int) const { return v; }
+};
+template <>
+struct BeamS0<true> {
+  const int* seq_len;  // [B * NB]
+  VCAP_DEV int of(int row) const { return seq_len[row]; }
+};
+
+template <int NB, int NC, bool PER_SEQ = false>   // NC: candidates per lane (NB * C * K <= 64 * NC)
 __global__ __launch_bounds__(512) void vcap_beam_select_kernel(BeamState st, int B, int L, int V, int C,
-                                                                int cur, int eos, float lpen, int S0, int anc_ld) {
+                                                                int cur, int eos, float lpen, BeamS0<PER_SEQ> s0,
+                                                                int anc_ld) {
   constexpr int K = 2 * NB;
   __shared__ int s_unsat[8], s_allhits[8];
   const int lane = threadIdx.x & 63, b = threadIdx.x >> 6;
@@ -357,7 +370,7 @@ __global__ __launch_bounds__(512) void vcap_beam_select_kernel(BeamState st, int
       }
     }
     // ---- writes
-    const int pos = S0 + cur;   // the next forward writes this position (own physical row)
+    const int pos = s0.of(b * NB) + cur;   // the next forward writes this position (own physical row)
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const int src = nxt_src[i];
@@ -441,22 +454,28 @@ hipError_t vcap_beam_cand_dispatch(const BeamState& st, const float* logits, con
 }
 
 hipError_t vcap_beam_select_dispatch(const BeamState& st, int B, int nb, int L, int V, int chunks, int cur, int eos,
-                                     float length_penalty, int S0, int anc_ld, hipStream_t s) {
+                                     float length_penalty, int S0, int anc_ld, hipStream_t s, const int* seq_len) {
   const int ncand = nb * chunks * 2 * nb;
   if (B > 8 || nb > 8 || 2 * nb > kMaxK || L > 64 || anc_ld > 128 || ncand > kSelNcMax * 64)
     return hipErrorInvalidValue;
-#define VCAP_SEL(NB)                                                                                          \
-  if (nb == NB) {                                                                                             \
+#define VCAP_SEL_AT(NB, PS, S0ARG)                                                                            \
+  {                                                                                                           \
     if (ncand <= select_nc(NB) * 64)                                                                          \
-      hipLaunchKernelGGL((vcap_beam_select_kernel<NB, select_nc(NB)>), dim3(1), dim3(64 * B), 0, s, st, B, L, V, \
-                         chunks, cur, eos, length_penalty, S0, anc_ld);                                       \
+      hipLaunchKernelGGL((vcap_beam_select_kernel<NB, select_nc(NB), PS>), dim3(1), dim3(64 * B), 0, s, st, B, L, V, \
+                         chunks, cur, eos, length_penalty, S0ARG, anc_ld);                                    \
     else                                                                                                      \
-      hipLaunchKernelGGL((vcap_beam_select_kernel<NB, kSelNcMax>), dim3(1), dim3(64 * B), 0, s, st, B, L, V,    \
-                         chunks, cur, eos, length_penalty, S0, anc_ld);                                       \
+      hipLaunchKernelGGL((vcap_beam_select_kernel<NB, kSelNcMax, PS>), dim3(1), dim3(64 * B), 0, s, st, B, L, V, \
+                         chunks, cur, eos, length_penalty, S0ARG, anc_ld);                                    \
     return hipGetLastError();                                                                                 \
+  }
+#define VCAP_SEL(NB)                                                      \
+  if (nb == NB) {                                                         \
+    if (seq_len) VCAP_SEL_AT(NB, true, BeamS0<true>{seq_len})             \
+    VCAP_SEL_AT(NB, false, BeamS0<false>{S0})                             \
   }
   VCAP_SEL(2) VCAP_SEL(3) VCAP_SEL(4) VCAP_SEL(5) VCAP_SEL(6) VCAP_SEL(7) VCAP_SEL(8)
 #undef VCAP_SEL
+#undef VCAP_SEL_AT
   return hipErrorInvalidValue;
 }
 

@@ -171,6 +171,21 @@ VCAP_DEV void rows_epilogue(const RowsGemmArgs& a, int m0, const float (*red)[MT
           pool[(((long)page * a.H + head) * 16 + (pos & 15)) * 64 + d] = Num<T>::from_f(v);
         }
       }
+    } else if constexpr (EPI == EPI_QKV_ROWS) {
+      // EPI_QKV with the row's (sequence, position) from the row tables (ragged prompts)
+      if (ok) {
+        const int Ed = N / 3;
+        const int which = n / Ed, within_e = n - which * Ed;
+        if (which == 0) {
+          ((T*)a.q_out)[(long)m * Ed + within_e] = Num<T>::from_f(v);
+        } else {
+          const int head = within_e >> 6, d = within_e & 63;
+          const int seq = a.row_seq ? a.row_seq[m] : m, pos = a.row_pos[m] + a.pos_add;
+          const int page = seq * a.maxp + (pos >> 4);
+          T* pool = (T*)(which == 1 ? a.kc : a.vc);
+          pool[(((long)page * a.H + head) * 16 + (pos & 15)) * 64 + d] = Num<T>::from_f(v);
+        }
+      }
     } else if constexpr (EPI == EPI_RESID) {
       if (ok && mine) ((float*)a.out)[(long)m * a.ldo + n] = pre_res[q] + v;
     } else if constexpr (EPI == EPI_GELU) {
@@ -787,6 +802,44 @@ __global__ __launch_bounds__(256) void vcap_embed_tokens_kernel(const int* __res
   for (int c = threadIdx.x; c < E; c += 256) h[(long)r * E + c] = Num<T>::to_f(wte[(long)t * E + c]) + wpe[(long)pos * E + c];
 }
 
+// Ragged prompts: packed prefill rows, row m = position row_pos[m] of sequence r = row_seq[m]; sequence r
+// reads prefix row r / prefix_rep and the prompt ids[ids_off[r / prefix_rep] ..] (device memory).
+template <typename T>
+__global__ __launch_bounds__(256) void vcap_prefill_embed_rows_kernel(
+    const float* __restrict__ prefix, int P, const int* __restrict__ ids, const int* __restrict__ ids_off,
+    const int* __restrict__ row_seq, const int* __restrict__ row_pos, const T* __restrict__ wte,
+    const float* __restrict__ wpe, float* __restrict__ h, int E, int prefix_rep) {
+  const int m = blockIdx.x;
+  const int s = row_seq[m] / prefix_rep, i = row_pos[m];
+  const int tok = i < P ? 0 : ids[ids_off[s] + (i - P)];
+  for (int c = threadIdx.x; c < E; c += 256) {
+    float v = (i < P) ? prefix[((long)s * P + i) * E + c] : Num<T>::to_f(wte[(long)tok * E + c]);
+    h[(long)m * E + c] = v + wpe[(long)i * E + c];
+  }
+}
+
+// vcap_embed_tokens_kernel at a position per row: min(seq_len[r] + pos_add, npos - 1)
+template <typename T>
+__global__ __launch_bounds__(256) void vcap_embed_tokens_rows_kernel(const int* __restrict__ tok,
+                                                                     const T* __restrict__ wte,
+                                                                     const float* __restrict__ wpe,
+                                                                     float* __restrict__ h, int E,
+                                                                     const int* __restrict__ seq_len, int pos_add,
+                                                                     int npos) {
+  const int r = blockIdx.x;
+  const int t = tok[r], pos = min(seq_len[r] + pos_add, npos - 1);
+  for (int c = threadIdx.x; c < E; c += 256) h[(long)r * E + c] = Num<T>::to_f(wte[(long)t * E + c]) + wpe[(long)pos * E + c];
+}
+
+// dst[r] = src[rows[r]]: each sequence's last prefill row, gathered for the lm_head (ragged prompts)
+__global__ __launch_bounds__(256) void vcap_gather_rows_kernel(const float* __restrict__ src,
+                                                               const int* __restrict__ rows, float* __restrict__ dst,
+                                                               int E) {
+  const int r = blockIdx.x;
+  const long sr = rows[r];
+  for (int c = threadIdx.x; c < E; c += 256) dst[(long)r * E + c] = src[sr * E + c];
+}
+
 // KV-cache row permutation for beam search: dst row r <- src row src[r], positions [0, len),
 // every layer/head (contiguous [page][H][16][64] pools with identity page tables).
 template <typename T>
@@ -821,12 +874,25 @@ __global__ void vcap_decode_init_kernel(int* page_table, int B, int maxp, int* f
 // write the next input embedding wte[tok] + wpe[pos].
 // SCREEN (f32 decoders, greedy): the partials are those of the bf16 screen (ScreenArgs); the token is
 // the exact-f32 argmax over the tokens the screen's error bound cannot rule out.
-template <typename T, bool SCREEN>
+// ROWS (ragged prompts): the next input's position is per row, from NextPos<true>'s tables.
+template <bool ROWS>
+struct NextPos {
+  int pos;
+  VCAP_DEV int of(int) const { return pos; }
+};
+template <>
+struct NextPos<true> {
+  const int* seq_len;  // [B]
+  int pos_add, npos;
+  VCAP_DEV int of(int m) const { return min(seq_len[m] + pos_add, npos - 1); }
+};
+
+template <typename T, bool SCREEN, bool ROWS = false>
 __global__ __launch_bounds__(256) void vcap_decode_finalize_kernel(
     const float* __restrict__ part_val, const int* __restrict__ part_idx, int nblk, int step, int* finished,
     int* hist, int hist_ld, int* banned, int* nbanned, int ngram, int eos, int pad, int* out_ids, int out_ld,
-    const T* __restrict__ wte, const float* __restrict__ wpe, float* __restrict__ h, int E, int pos_next, int vocab,
-    ScreenArgs sc) {
+    const T* __restrict__ wte, const float* __restrict__ wpe, float* __restrict__ h, int E, NextPos<ROWS> next,
+    int vocab, ScreenArgs sc) {
   __shared__ float sv[4];
   __shared__ int si[4];
   __shared__ int s_h[1024];
@@ -1008,6 +1074,7 @@ __global__ __launch_bounds__(256) void vcap_decode_finalize_kernel(
   __syncthreads();
   if (tid == 0) nbanned[m] = s_nb;
   const int tok = s_tok;
+  const int pos_next = next.of(m);
   for (int c = tid; c < E; c += 256)
     h[(long)m * E + c] = Num<T>::to_f(wte[(long)tok * E + c]) + wpe[(long)pos_next * E + c];
 }
@@ -1498,6 +1565,7 @@ hipError_t vcap_rows_gemm_dispatch(int dt, int pro, int epi, const RowsGemmArgs&
   VCAP_ROWS(TT, PP, EE, 1)
 #define VCAP_ROWS_EPI(TT)                                                                    \
   if (pro == PRO_LN && epi == EPI_QKV) { VCAP_ROWS_NT(TT, PRO_LN, EPI_QKV) }                \
+  if (pro == PRO_LN && epi == EPI_QKV_ROWS) { VCAP_ROWS_NT(TT, PRO_LN, EPI_QKV_ROWS) }      \
   if (pro == PRO_LN && epi == EPI_GELU) { VCAP_ROWS_NT(TT, PRO_LN, EPI_GELU) }              \
   if (pro == PRO_DIRECT && epi == EPI_RESID) { VCAP_ROWS_NT(TT, PRO_DIRECT, EPI_RESID) }    \
   if (pro == PRO_DIRECT && epi == EPI_STORE && ntb == 1) { VCAP_ROWS(TT, PRO_DIRECT, EPI_STORE, 1) } \
@@ -1583,11 +1651,11 @@ hipError_t vcap_decode_init_dispatch(int* page_table, int B, int maxp, int* fini
   return hipGetLastError();
 }
 
-hipError_t vcap_decode_finalize_dispatch(int dt, const float* part_val, const int* part_idx, int nblk, int B,
-                                         int step, int* finished, int* hist, int hist_ld, int* banned, int* nbanned,
-                                         int ngram, int eos, int pad, int* out_ids, int out_ld, const void* wte,
-                                         const float* wpe, float* h, int E, int pos_next, int vocab, hipStream_t s,
-                                         const ScreenArgs* screen) {
+template <bool ROWS>
+static hipError_t launch_finalize(int dt, const float* part_val, const int* part_idx, int nblk, int B, int step,
+                                  int* finished, int* hist, int hist_ld, int* banned, int* nbanned, int ngram, int eos,
+                                  int pad, int* out_ids, int out_ld, const void* wte, const float* wpe, float* h,
+                                  int E, NextPos<ROWS> next, int vocab, hipStream_t s, const ScreenArgs* screen) {
   if (hist_ld > 1024 || nblk < 1 || nblk > 2048 || step >= hist_ld) return hipErrorInvalidValue;
   ScreenArgs sc{};
   if (screen) {
@@ -1597,16 +1665,68 @@ hipError_t vcap_decode_finalize_dispatch(int dt, const float* part_val, const in
     sc = *screen;
   }
   if (dt == VCAP_DT_BF16)
-    hipLaunchKernelGGL((vcap_decode_finalize_kernel<bf16_t, false>), dim3(B), dim3(256), 0, s, part_val, part_idx,
-                       nblk, step, finished, hist, hist_ld, banned, nbanned, ngram, eos, pad, out_ids, out_ld,
-                       (const bf16_t*)wte, wpe, h, E, pos_next, vocab, sc);
+    hipLaunchKernelGGL((vcap_decode_finalize_kernel<bf16_t, false, ROWS>), dim3(B), dim3(256), 0, s, part_val,
+                       part_idx, nblk, step, finished, hist, hist_ld, banned, nbanned, ngram, eos, pad, out_ids, out_ld,
+                       (const bf16_t*)wte, wpe, h, E, next, vocab, sc);
   else if (screen)
-    hipLaunchKernelGGL((vcap_decode_finalize_kernel<float, true>), dim3(B), dim3(256), 0, s, part_val, part_idx,
+    hipLaunchKernelGGL((vcap_decode_finalize_kernel<float, true, ROWS>), dim3(B), dim3(256), 0, s, part_val, part_idx,
                        nblk, step, finished, hist, hist_ld, banned, nbanned, ngram, eos, pad, out_ids, out_ld,
-                       (const float*)wte, wpe, h, E, pos_next, vocab, sc);
+                       (const float*)wte, wpe, h, E, next, vocab, sc);
   else
-    hipLaunchKernelGGL((vcap_decode_finalize_kernel<float, false>), dim3(B), dim3(256), 0, s, part_val, part_idx,
+    hipLaunchKernelGGL((vcap_decode_finalize_kernel<float, false, ROWS>), dim3(B), dim3(256), 0, s, part_val, part_idx,
                        nblk, step, finished, hist, hist_ld, banned, nbanned, ngram, eos, pad, out_ids, out_ld,
-                       (const float*)wte, wpe, h, E, pos_next, vocab, sc);
+                       (const float*)wte, wpe, h, E, next, vocab, sc);
+  return hipGetLastError();
+}
+
+hipError_t vcap_decode_finalize_dispatch(int dt, const float* part_val, const int* part_idx, int nblk, int B,
+                                         int step, int* finished, int* hist, int hist_ld, int* banned, int* nbanned,
+                                         int ngram, int eos, int pad, int* out_ids, int out_ld, const void* wte,
+                                         const float* wpe, float* h, int E, int pos_next, int vocab, hipStream_t s,
+                                         const ScreenArgs* screen) {
+  return launch_finalize<false>(dt, part_val, part_idx, nblk, B, step, finished, hist, hist_ld, banned, nbanned, ngram,
+                                eos, pad, out_ids, out_ld, wte, wpe, h, E, NextPos<false>{pos_next}, vocab, s, screen);
+}
+
+hipError_t vcap_decode_finalize_rows_dispatch(int dt, const float* part_val, const int* part_idx, int nblk, int B,
+                                              int step, int* finished, int* hist, int hist_ld, int* banned,
+                                              int* nbanned, int ngram, int eos, int pad, int* out_ids, int out_ld,
+                                              const void* wte, const float* wpe, float* h, int E, const int* seq_len,
+                                              int pos_add, int npos, int vocab, hipStream_t s,
+                                              const ScreenArgs* screen) {
+  if (!seq_len || npos <= 0) return hipErrorInvalidValue;
+  return launch_finalize<true>(dt, part_val, part_idx, nblk, B, step, finished, hist, hist_ld, banned, nbanned, ngram,
+                               eos, pad, out_ids, out_ld, wte, wpe, h, E, NextPos<true>{seq_len, pos_add, npos}, vocab,
+                               s, screen);
+}
+
+hipError_t vcap_prefill_embed_rows_dispatch(int dt, const float* prefix, int P, const int* ids, const int* ids_off,
+                                            const int* row_seq, const int* row_pos, const void* wte, const float* wpe,
+                                            float* h, int M, int E, int prefix_rep, hipStream_t s) {
+  if (M <= 0 || prefix_rep <= 0 || !ids_off || !row_seq || !row_pos) return hipErrorInvalidValue;
+  if (dt == VCAP_DT_BF16)
+    hipLaunchKernelGGL((vcap_prefill_embed_rows_kernel<bf16_t>), dim3(M), dim3(256), 0, s, prefix, P, ids, ids_off,
+                       row_seq, row_pos, (const bf16_t*)wte, wpe, h, E, prefix_rep);
+  else
+    hipLaunchKernelGGL((vcap_prefill_embed_rows_kernel<float>), dim3(M), dim3(256), 0, s, prefix, P, ids, ids_off,
+                       row_seq, row_pos, (const float*)wte, wpe, h, E, prefix_rep);
+  return hipGetLastError();
+}
+
+hipError_t vcap_embed_tokens_rows_dispatch(int dt, const int* tok, int rows, const void* wte, const float* wpe,
+                                           float* h, int E, const int* seq_len, int pos_add, int npos, hipStream_t s) {
+  if (!seq_len || npos <= 0) return hipErrorInvalidValue;
+  if (dt == VCAP_DT_BF16)
+    hipLaunchKernelGGL((vcap_embed_tokens_rows_kernel<bf16_t>), dim3(rows), dim3(256), 0, s, tok, (const bf16_t*)wte,
+                       wpe, h, E, seq_len, pos_add, npos);
+  else
+    hipLaunchKernelGGL((vcap_embed_tokens_rows_kernel<float>), dim3(rows), dim3(256), 0, s, tok, (const float*)wte, wpe,
+                       h, E, seq_len, pos_add, npos);
+  return hipGetLastError();
+}
+
+hipError_t vcap_gather_rows_dispatch(const float* src, const int* rows, float* dst, int R, int E, hipStream_t s) {
+  if (R <= 0 || !rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(vcap_gather_rows_kernel, dim3(R), dim3(256), 0, s, src, rows, dst, E);
   return hipGetLastError();
 }

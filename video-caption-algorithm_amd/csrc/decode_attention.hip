@@ -96,6 +96,40 @@ struct KeyMask<true> {
   VCAP_DEV bool hidden(int seq, int j) const { return m[(long)seq * ld + j] == 0; }
 };
 
+// Row positions: which sequence row m belongs to and the position its query sits at (ctx = position + 1).
+// UniformRows is (S_new, past): sequence m / S_new, position past + m % S_new - every call with one prompt
+// for the batch.  TableRows reads them (ragged prompts): sequence row_seq[m] (nullptr: m), position
+// row_pos[m] + pos_add, so rows of one launch stop at contexts of their own; each item still runs the
+// same loop to its own ctx, in the same order.
+// The two kernel forms do not give the same f32 bits, and a one-prompt call picks its form by the
+// sequence's length at the launch (past + S_new <= 64).  A ragged launch keeps every row on the form its
+// own one-prompt call takes: mine() passes the rows whose sequence length is in (lo, hi], and a launch
+// with sequences on both sides of 64 runs both kernels, each on its own rows.
+struct UniformRows {
+  int S_new, past;
+  VCAP_DEV void locate(int m, bool single, int& seq, int& qpos) const {
+    const int S = single ? 1 : S_new;
+    seq = m / S;
+    qpos = past + (m - seq * S);
+  }
+  VCAP_DEV bool mine(int, int) const { return true; }
+};
+struct TableRows {
+  const int* row_seq;
+  const int* row_pos;
+  int pos_add;
+  const int* seq_len;  // [seqs] with row_seq (a packed prefill: the sequence's S0); else the row's own ctx
+  int lo, hi;
+  VCAP_DEV void locate(int m, bool, int& seq, int& qpos) const {
+    seq = row_seq ? row_seq[m] : m;
+    qpos = row_pos[m] + pos_add;
+  }
+  VCAP_DEV bool mine(int seq, int ctx) const {
+    const int len = row_seq ? seq_len[seq] : ctx;
+    return len > lo && len <= hi;
+  }
+};
+
 // ------------------------------------------------------------------------------------------------
 // the E8 elements of a 16-byte chunk as floats, in memory order
 template <typename T>
@@ -131,11 +165,11 @@ VCAP_DEV void store_out8(T* orow, const float (&o)[8], float inv) {
 // Any context up to 1024 (the dispatcher's bound: s_p).  4 items per 256-thread workgroup.
 // Scores: lane j <-> key j (+64 ...), full 64-dim dot.  P.V: lane = (key group kg of 8, 8
 // consecutive dims d8), partial sums reduced over the 8 key groups by DPP + permlane swaps.
-template <typename T, typename Keys, bool MASKED>
+template <typename T, typename Keys, bool MASKED, typename Rows = UniformRows>
 __global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __restrict__ q, const T* __restrict__ kc,
                                                                     const T* __restrict__ vc, Keys keys,
-                                                                    T* __restrict__ out, int M, int H, int S_new,
-                                                                    int past, KeyMask<MASKED> km) {
+                                                                    T* __restrict__ out, int M, int H, Rows rows,
+                                                                    KeyMask<MASKED> km) {
   constexpr int E8 = Frag<T>::kElems;  // elements per 16-byte chunk
   __shared__ float s_q[4][64];
   __shared__ float s_p[4][1024];
@@ -144,9 +178,10 @@ __global__ __launch_bounds__(256) void vcap_decode_attention_kernel(const T* __r
   if (item >= M * H) return;
   const int m = item / H, h = item - m * H;
   const int E = H * 64;
-  const int S = Keys::kSingleQuery ? 1 : S_new;
-  const int seq = m / S, qpos = past + (m - seq * S);
+  int seq, qpos;
+  rows.locate(m, Keys::kSingleQuery, seq, qpos);
   const int ctx = qpos + 1;
+  if (!rows.mine(seq, ctx)) return;
   const auto ki = keys.item(seq, m);
   s_q[wave][lane] = Num<T>::to_f(q[(long)m * E + h * 64 + lane]);
   __builtin_amdgcn_wave_barrier();
@@ -302,10 +337,10 @@ VCAP_DEV void c64_finish(const C64Loads<T>& L, float* s_q, float* s_p, int ctx, 
 }
 
 // WAVES items per 64 * WAVES-thread workgroup (the launch site chooses per key source).
-template <typename T, typename Keys, bool MASKED, int WAVES>
+template <typename T, typename Keys, bool MASKED, int WAVES, typename Rows = UniformRows>
 __global__ __launch_bounds__(64 * WAVES) void vcap_decode_attention_c64_kernel(
     const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc, Keys keys, T* __restrict__ out, int M,
-    int H, int S_new, int past, KeyMask<MASKED> km) {
+    int H, Rows rows, KeyMask<MASKED> km) {
   __shared__ __attribute__((aligned(16))) float s_q[WAVES][64];
   __shared__ float s_p[WAVES][64];
   __shared__ int s_a[Keys::kStaged ? WAVES : 1][64];
@@ -313,9 +348,10 @@ __global__ __launch_bounds__(64 * WAVES) void vcap_decode_attention_c64_kernel(
   const int item = blockIdx.x * WAVES + wave;
   if (item >= M * H) return;
   const int m = item / H, h = item - m * H;
-  const int S = Keys::kSingleQuery ? 1 : S_new;
-  const int seq = m / S, qpos = past + (m - seq * S);
+  int seq, qpos;
+  rows.locate(m, Keys::kSingleQuery, seq, qpos);
   const int ctx = qpos + 1;
+  if (!rows.mine(seq, ctx)) return;
   C64Loads<T> L;
   c64_issue<T>(L, q, kc, vc, keys, seq, m, h, H, ctx, s_q[wave], s_a[wave]);
   bool vis = true;
@@ -331,11 +367,38 @@ static hipError_t launch_decode_attention(const void* q, const void* kc, const v
                                           void* out, int M, int H, int S_new, int past, hipStream_t s,
                                           KeyMask<MASKED> km) {
   const bool c64 = past + S_new <= 64;
-  auto launch = [&](auto kernel, int waves, auto keys) {
+  auto launch_rows = [&](auto kernel, int waves, auto keys, auto rows) {
     hipLaunchKernelGGL(kernel, dim3((M * H + waves - 1) / waves), dim3(64 * waves), 0, s, (const T*)q, (const T*)kc,
-                       (const T*)vc, keys, (T*)out, M, H, S_new, past, km);
+                       (const T*)vc, keys, (T*)out, M, H, rows, km);
     return hipGetLastError();
   };
+  auto launch = [&](auto kernel, int waves, auto keys) { return launch_rows(kernel, waves, keys, UniformRows{S_new, past}); };
+  if constexpr (!MASKED)
+    if (k.row_pos) {
+      // ragged prompts: the same four kernels with the row tables.  past + 1 is the launch's longest
+      // sequence, k.min_len its shortest: sequences of <= 64 take the <= 64 form, longer ones the general
+      // form, as their one-prompt calls do - two launches when the launch holds both
+      const bool any64 = k.min_len <= 64, any_long = !c64;
+      if (k.row_seq && !k.seq_len) return hipErrorInvalidValue;
+      if (any_long && !k.anc && !k.page_table) return hipErrorInvalidValue;
+      const TableRows r64{k.row_seq, k.row_pos, k.pos_add, k.seq_len, 0, 64};
+      const TableRows rlong{k.row_seq, k.row_pos, k.pos_add, k.seq_len, 64, 0x7fffffff};
+      hipError_t err = hipSuccess;
+      if (k.anc) {
+        const AncestryKeys keys{k.anc, k.anc_ld, maxp};
+        if (any64) err = launch_rows(vcap_decode_attention_c64_kernel<T, AncestryKeys, false, 4, TableRows>, 4, keys, r64);
+        if (any_long && err == hipSuccess)
+          err = launch_rows(vcap_decode_attention_kernel<T, AncestryKeys, false, TableRows>, 4, keys, rlong);
+        return err;
+      }
+      if (any64)
+        err = launch_rows(vcap_decode_attention_c64_kernel<T, ContiguousKeys, false, 1, TableRows>, 1,
+                          ContiguousKeys{maxp}, r64);
+      if (any_long && err == hipSuccess)
+        err = launch_rows(vcap_decode_attention_kernel<T, PagedKeys, false, TableRows>, 4,
+                          PagedKeys{k.page_table, maxp}, rlong);
+      return err;
+    }
   if constexpr (!MASKED)
     if (k.anc) {
       const AncestryKeys keys{k.anc, k.anc_ld, maxp};
@@ -353,6 +416,7 @@ hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc,
                                           int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s) {
   if (past + S_new > 1024) return hipErrorInvalidValue;
   if (k.anc ? (S_new != 1 || past + 1 > k.anc_ld || k.kmask) : maxp > 64) return hipErrorInvalidValue;
+  if (k.row_pos && (S_new != 1 || k.kmask || k.min_len < 1 || k.min_len > past + 1)) return hipErrorInvalidValue;
   const bool bf16 = dt == VCAP_DT_BF16;
   if (!k.kmask) {
     const KeyMask<false> km{};

@@ -6,6 +6,7 @@
 // The reference drives these steps from Python (HF generate); here the whole schedule is native so one
 // ABI call issues the full decode (~60 launches per token), captured once into a hipGraph and replayed.
 #include <algorithm>
+#include <vector>
 
 #include "runtime_common.h"
 
@@ -45,10 +46,13 @@ struct DecState {
 
 int max_logit_blocks(int V, int B) { return vcap_logit_blocks(V, B); }
 
-DecState carve_dec(Carver& c, const vcap_gpt2_desc* d, int B, int S0, int max_new) {
+// prefill_rows > 0 (ragged prompts): the prefill packs that many rows instead of B * S0, and S0 (the
+// longest sequence's) sizes the pages only
+DecState carve_dec(Carver& c, const vcap_gpt2_desc* d, int B, int S0, int max_new, int prefill_rows = 0) {
   const int E = d->n_embd;
   const size_t es = esize(d->dtype);
-  const size_t Mmax = (size_t)B * S0 > (size_t)B ? (size_t)B * S0 : B;
+  const size_t M0 = prefill_rows > 0 ? (size_t)prefill_rows : (size_t)B * S0;
+  const size_t Mmax = M0 > (size_t)B ? M0 : B;
   DecState b;
   b.maxp = (S0 + max_new + 15) / 16;
   const size_t pages = (size_t)B * b.maxp;
@@ -127,6 +131,13 @@ struct LayerExtras {
   int anc_ld = 0;
   const uint8_t* kmask = nullptr;
   int mask_ld = 0;
+  // ragged prompts: row m is position row_pos[m] + pos_add of sequence row_seq[m] (nullptr: m); run_layers
+  // is then called with S_new = 1 and past + 1 = the largest context of the launch
+  const int* row_seq = nullptr;
+  const int* row_pos = nullptr;
+  int pos_add = 0;
+  const int* seq_len = nullptr;   // [seqs], with row_seq
+  int min_len = 0;                // the shortest sequence of the launch (past + 1 is the longest)
 };
 
 int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int past, int max_blocks, hipStream_t s,
@@ -148,12 +159,14 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
     // pages are allocated contiguously per sequence (identity table written by vcap_decode_init):
     // the scatter computes page ids instead of loading them (nullptr table)
     a.page_table = nullptr; a.maxp = w.maxp; a.H = H; a.S_new = S_new; a.past = past; a.max_blocks = max_blocks;
-    VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_LN, EPI_QKV, a, nullptr, s), "c_attn");
+    a.row_seq = x.row_seq; a.row_pos = x.row_pos; a.pos_add = x.pos_add;
+    VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_LN, x.row_pos ? EPI_QKV_ROWS : EPI_QKV, a, nullptr, s), "c_attn");
     // 2) causal attention over the paged cache
     // pages are allocated contiguously per sequence (vcap_decode_init: identity table), so the
     // short-context kernels (bf16 and f32) compute page ids instead of loading them (nullptr table);
     // beam search reads through its ancestry table instead
-    const DecodeKeys keys{x.anc || past + S_new <= 64 ? nullptr : w.pt, x.anc, x.anc_ld, x.kmask, x.mask_ld};
+    const DecodeKeys keys{x.anc || past + S_new <= 64 ? nullptr : w.pt, x.anc, x.anc_ld, x.kmask, x.mask_ld,
+                          x.row_seq, x.row_pos, x.pos_add, x.seq_len, x.min_len};
     VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, keys, w.maxp, w.attn, M, H, S_new, past, s),
              "decode_attention");
     // 3) attn c_proj + residual
@@ -210,6 +223,99 @@ int run_raw_forward(const vcap_gpt2_desc* d, const DecState& w, int rows, int S_
   return 0;
 }
 
+// ---- ragged prompts: B prompts of their own lengths in one decode.  R = B * rep row-sequences (rep =
+// num_beams for the search's replicated prefill, else 1); sequence r carries prompt r / rep and
+// S0[r / rep] = prefix_len + len positions; the prefill packs the sequences' rows back to back.
+struct Ragged {
+  int B = 0, rep = 1, R = 0, M = 0, nids = 0, max_S0 = 0, min_S0 = 0;
+  const int* offsets = nullptr;  // host [B + 1]
+  // device, carved from the workspace: one int block [row_seq M | row_pos M | seq_len R | last_row R |
+  // ids_off B | ids nids] (uploaded in one copy) and the gathered last prefill rows
+  int* tab = nullptr;
+  float* hl = nullptr;
+  int* row_seq() const { return tab; }
+  int* row_pos() const { return tab + M; }
+  int* seq_len() const { return tab + 2 * M; }
+  int* last_row() const { return tab + 2 * M + R; }
+  int* ids_off() const { return tab + 2 * M + 2 * R; }
+  int* ids() const { return tab + 2 * M + 2 * R + B; }
+  size_t tab_ints() const { return (size_t)2 * M + 2 * R + B + nids; }
+};
+
+// The shape checks every ragged entry point and workspace query share (the limits in include/vcap.h).
+// s0_zero_code: what an empty sequence is (the uniform generate / beam search: UNSUPPORTED, sample: ARG).
+int ragged_shape(const char* name, const vcap_gpt2_desc* d, const int* offsets, int B, int max_new, int rep,
+                 int s0_zero_code, Ragged* out) {
+  if (!offsets || B <= 0 || offsets[0] != 0) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments");
+  Ragged r;
+  r.B = B; r.rep = rep; r.R = B * rep; r.offsets = offsets;
+  long M = 0;
+  for (int b = 0; b < B; ++b) {
+    const long len = (long)offsets[b + 1] - offsets[b];
+    if (len < 0) return fail(VCAP_E_ARG, std::string(name) + ": prompt offsets must be non-decreasing");
+    if (len > 64) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments (a prompt over 64 ids)");
+    const int S0 = d->prefix_len + (int)len;
+    if (S0 <= 0) return fail(s0_zero_code, std::string(name) + ": a sequence with no prefix and no prompt");
+    if (S0 + max_new > d->n_positions) return fail(VCAP_E_UNSUPPORTED, "context exceeds n_positions");
+    r.max_S0 = std::max(r.max_S0, S0);
+    r.min_S0 = b == 0 ? S0 : std::min(r.min_S0, S0);
+    M += (long)S0 * rep;
+    if (M > kMaxDecodeRows) return fail(VCAP_E_UNSUPPORTED, "sum of (prefix+prompt) rows exceeds vcap_gpt2_max_rows()");
+  }
+  r.M = (int)M;
+  r.nids = offsets[B];
+  *out = r;
+  return 0;
+}
+
+int ragged_ids(const char* name, const vcap_gpt2_desc* d, const vcap_prompts* p, const Ragged& r) {
+  if (r.nids && !p->ids) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments");
+  return check_prompt_ids(d, p->ids, r.nids);
+}
+
+void carve_ragged(Carver& c, const vcap_gpt2_desc* d, Ragged& r) {
+  r.tab = (int*)c.take(r.tab_ints() * 4);
+  r.hl = (float*)c.take((size_t)r.R * d->n_embd * 4);
+}
+
+// Tables + ids to the workspace, on the call's stream and outside any captured graph (like the Philox
+// seed): a captured graph bakes in the shape only.  The host block is pageable memory, so the copy has
+// left it when hipMemcpyAsync returns; it is kept per thread all the same.
+int upload_ragged(const vcap_gpt2_desc* d, const Ragged& r, const int* ids, hipStream_t s) {
+  thread_local std::vector<int> host;
+  host.assign(r.tab_ints(), 0);
+  int* row_seq = host.data();
+  int* row_pos = row_seq + r.M;
+  int* seq_len = row_pos + r.M;
+  int* last_row = seq_len + r.R;
+  int* ids_off = last_row + r.R;
+  int m = 0;
+  for (int q = 0; q < r.R; ++q) {
+    const int b = q / r.rep, S0 = d->prefix_len + r.offsets[b + 1] - r.offsets[b];
+    for (int i = 0; i < S0; ++i, ++m) {
+      row_seq[m] = q;
+      row_pos[m] = i;
+    }
+    seq_len[q] = S0;
+    last_row[q] = m - 1;
+  }
+  for (int b = 0; b < r.B; ++b) ids_off[b] = r.offsets[b];
+  for (int i = 0; i < r.nids; ++i) ids_off[r.B + i] = ids[i];
+  VCAP_TRY(hipMemcpyAsync(r.tab, host.data(), host.size() * 4, hipMemcpyHostToDevice, s), "ragged tables");
+  return 0;
+}
+
+// run_layers' extras for the packed prefill and for step `t` (the t-th token after the prefill's)
+LayerExtras ragged_prefill_rows(const Ragged& r) {
+  LayerExtras x;
+  x.row_seq = r.row_seq(); x.row_pos = r.row_pos(); x.seq_len = r.seq_len(); x.min_len = r.min_S0;
+  return x;
+}
+LayerExtras ragged_step_rows(const Ragged& r, int t, LayerExtras x = {}) {
+  x.row_seq = nullptr; x.row_pos = r.seq_len(); x.pos_add = t; x.min_len = r.min_S0 + t + 1;
+  return x;
+}
+
 // What vcap_gpt2_generate / _sample / _beam_search were given: issue_decode and issue_beam launch from
 // it and the graph key is made of it.  Greedy: gp.  Sampling: gp + sp.  Beam search: bp + out_len.
 struct DecodeCall {
@@ -225,6 +331,7 @@ struct DecodeCall {
   const int* force_ids = nullptr;
   const vcap_beam_params* bp = nullptr;
   int* out_len = nullptr;
+  const Ragged* rg = nullptr;   // the _ragged entry points: ids / nids unused
 };
 
 // sp != nullptr: sampling mode (HF _sample): the lm_head also stores the processed scores, the
@@ -234,16 +341,32 @@ int issue_decode(const DecodeCall& c, const DecState& w, hipStream_t s) {
   const vcap_gen_params* gp = c.gp;
   const vcap_sample_params* sp = c.sp;
   const int E = d->n_embd, V = d->vocab, B = c.B;
-  const int P = d->prefix_len, S0 = P + c.nids, max_new = gp->max_new_tokens;
+  const Ragged* rg = c.rg;
+  const int P = d->prefix_len, S0 = rg ? rg->max_S0 : P + c.nids, max_new = gp->max_new_tokens;
   const int dt = d->dtype;
   VCAP_TRY(vcap_decode_init_dispatch(w.pt, B, w.maxp, w.finished, w.nbanned, s, w.skc, w.n_skc), "decode_init");
-  VCAP_TRY(vcap_prefill_embed_dispatch(dt, c.prefix, P, c.ids, c.nids, d->wte, d->wpe, w.h, B, E, s), "prefill_embed");
+  if (rg)
+    VCAP_TRY(vcap_prefill_embed_rows_dispatch(dt, c.prefix, P, rg->ids(), rg->ids_off(), rg->row_seq(), rg->row_pos(),
+                                              d->wte, d->wpe, w.h, rg->M, E, 1, s),
+             "prefill_embed_rows");
+  else
+    VCAP_TRY(vcap_prefill_embed_dispatch(dt, c.prefix, P, c.ids, c.nids, d->wte, d->wpe, w.h, B, E, s), "prefill_embed");
   for (int step = 0; step < max_new; ++step) {
-    const int S_new = step == 0 ? S0 : 1;
-    const int past = step == 0 ? 0 : S0 + step - 1;
-    if (int rc = run_layers(d, w, B * S_new, S_new, past, gp->max_blocks, s)) return rc;
+    // ragged: every row is a "sequence of one row" whose position comes from the tables
+    const int S_new = step == 0 && !rg ? S0 : 1;
+    const int past = step == 0 ? (rg ? S0 - 1 : 0) : S0 + step - 1;   // ragged: the largest context - 1
+    if (!rg) {
+      if (int rc = run_layers(d, w, B * S_new, S_new, past, gp->max_blocks, s)) return rc;
+    } else if (step == 0) {
+      if (int rc = run_layers(d, w, rg->M, 1, past, gp->max_blocks, s, ragged_prefill_rows(*rg))) return rc;
+      // the lm_head reads each sequence's last prefill row from a contiguous copy
+      VCAP_TRY(vcap_gather_rows_dispatch(w.h, rg->last_row(), rg->hl, B, E, s), "gather_last_rows");
+    } else {
+      if (int rc = run_layers(d, w, B, 1, past, gp->max_blocks, s, ragged_step_rows(*rg, step - 1))) return rc;
+    }
     int nblk = 0;
     RowsGemmArgs g = logits_args(d, w, B, S_new, max_new, step);
+    if (rg && step == 0) g.x = rg->hl;
     g.rep_penalty = gp->repetition_penalty; g.min_new = gp->min_new_tokens; g.eos = gp->eos_token_id;
     // f32 greedy: the bf16 lm_head screens, the finalize rescores the survivors in f32 (exact argmax);
     // requested raw logits or sampling need every f32 score - the f32 lm_head then
@@ -276,12 +399,19 @@ int issue_decode(const DecodeCall& c, const DecState& w, hipStream_t s) {
       VCAP_TRY(vcap_sample_dispatch(sa, B, s), "sample");
       nblk = 1;
     }
-    VCAP_TRY(vcap_decode_finalize_dispatch(dt, w.pval, w.pidx, nblk, B, step, w.finished, w.hist, max_new, w.banned,
-                                           w.nbanned, gp->no_repeat_ngram_size, gp->eos_token_id, gp->pad_token_id,
-                                           c.out_ids, max_new, d->wte, d->wpe, w.h, E,
-                                           (S0 + step) < d->n_positions ? S0 + step : d->n_positions - 1, V, s,
-                                           screen ? &sc : nullptr),
-             "finalize");
+    if (rg)
+      VCAP_TRY(vcap_decode_finalize_rows_dispatch(dt, w.pval, w.pidx, nblk, B, step, w.finished, w.hist, max_new,
+                                                  w.banned, w.nbanned, gp->no_repeat_ngram_size, gp->eos_token_id,
+                                                  gp->pad_token_id, c.out_ids, max_new, d->wte, d->wpe, w.h, E,
+                                                  rg->seq_len(), step, d->n_positions, V, s, screen ? &sc : nullptr),
+               "finalize_rows");
+    else
+      VCAP_TRY(vcap_decode_finalize_dispatch(dt, w.pval, w.pidx, nblk, B, step, w.finished, w.hist, max_new, w.banned,
+                                             w.nbanned, gp->no_repeat_ngram_size, gp->eos_token_id, gp->pad_token_id,
+                                             c.out_ids, max_new, d->wte, d->wpe, w.h, E,
+                                             (S0 + step) < d->n_positions ? S0 + step : d->n_positions - 1, V, s,
+                                             screen ? &sc : nullptr),
+               "finalize");
   }
   return 0;
 }
@@ -294,8 +424,14 @@ std::string decode_key(const DecodeCall& c, const void* workspace) {
   if (c.bp) k.put(c.bp, sizeof(*c.bp));
   else k.put(c.gp, sizeof(*c.gp));
   k.val(c.prefix);
-  k.put(c.ids, sizeof(int) * (size_t)c.nids);
-  k.val(c.nids);
+  if (c.rg) {
+    // the ids live in the workspace (uploaded outside the graph): the shape alone is baked in
+    k.put("ragged", 6);
+    k.put(c.rg->offsets, sizeof(int) * (size_t)(c.B + 1));
+  } else {
+    k.put(c.ids, sizeof(int) * (size_t)c.nids);
+    k.val(c.nids);
+  }
   k.val(c.B);
   k.val(c.out_ids);
   if (c.bp) k.val(c.out_len);
@@ -313,6 +449,17 @@ std::string decode_key(const DecodeCall& c, const void* workspace) {
   return k.k;
 }
 
+// The seed upload, then the launch: eager, or the cached graph's replay.
+int run_decode_carved(const DecodeCall& c, const DecState& w, void* workspace, hipStream_t s) {
+  if (c.sp) {
+    // the Philox key goes to device memory outside the graph: one captured graph serves every seed
+    VCAP_TRY(hipMemsetD32Async((hipDeviceptr_t)w.seed, (int)(uint32_t)c.sp->seed, 1, s), "seed lo");
+    VCAP_TRY(hipMemsetD32Async((hipDeviceptr_t)(w.seed + 1), (int)(uint32_t)(c.sp->seed >> 32), 1, s), "seed hi");
+  }
+  if (!c.gp->use_graph) return issue_decode(c, w, s);
+  return launch_cached(decode_key(c, workspace), s, [&](hipStream_t cs) { return issue_decode(c, w, cs); });
+}
+
 // The checked call of vcap_gpt2_generate / vcap_gpt2_sample (`name`): carve, then launch eagerly or
 // replay the cached graph.
 int run_decode(const char* name, const DecodeCall& c, void* workspace, size_t ws_bytes, hipStream_t s) {
@@ -321,13 +468,19 @@ int run_decode(const char* name, const DecodeCall& c, void* workspace, size_t ws
     return fail(VCAP_E_WORKSPACE, std::string(name) + ": workspace too small");
   Carver cv(workspace);
   const DecState w = carve_dec(cv, c.d, c.B, S0, max_new);
-  if (c.sp) {
-    // the Philox key goes to device memory outside the graph: one captured graph serves every seed
-    VCAP_TRY(hipMemsetD32Async((hipDeviceptr_t)w.seed, (int)(uint32_t)c.sp->seed, 1, s), "seed lo");
-    VCAP_TRY(hipMemsetD32Async((hipDeviceptr_t)(w.seed + 1), (int)(uint32_t)(c.sp->seed >> 32), 1, s), "seed hi");
-  }
-  if (!c.gp->use_graph) return issue_decode(c, w, s);
-  return launch_cached(decode_key(c, workspace), s, [&](hipStream_t cs) { return issue_decode(c, w, cs); });
+  return run_decode_carved(c, w, workspace, s);
+}
+
+// ... and of the _ragged forms (rg checked by ragged_shape / ragged_ids): the tables follow the decode state
+int run_decode_ragged(const char* name, DecodeCall c, Ragged rg, const int* ids, void* workspace, size_t ws_bytes,
+                      hipStream_t s) {
+  Carver cv(workspace);
+  const DecState w = carve_dec(cv, c.d, c.B, rg.max_S0, c.gp->max_new_tokens, rg.M);
+  carve_ragged(cv, c.d, rg);
+  if (ws_bytes < cv.off) return fail(VCAP_E_WORKSPACE, std::string(name) + ": workspace too small");
+  if (int rc = upload_ragged(c.d, rg, ids, s)) return rc;
+  c.rg = &rg;
+  return run_decode_carved(c, w, workspace, s);
 }
 
 // ---- the step path (host-bookkeeping beam search): the decode state plus the reorder's scratch pool
@@ -364,10 +517,11 @@ struct BeamBufs {
   int nblk, chunks, anc_ld;
 };
 
-BeamBufs carve_beam(Carver& c, const vcap_gpt2_desc* d, int B, int nb, int S0, int L) {
+// prefill_rows > 0 (ragged prompts): S0 is the longest sequence's, see carve_dec
+BeamBufs carve_beam(Carver& c, const vcap_gpt2_desc* d, int B, int nb, int S0, int L, int prefill_rows = 0) {
   BeamBufs b;
   const int R = B * nb;
-  b.w = carve_dec(c, d, R, S0, L);
+  b.w = carve_dec(c, d, R, S0, L, prefill_rows);
   b.nblk = max_logit_blocks(d->vocab, R);
   b.chunks = vcap_beam_chunks(d->vocab);
   b.anc_ld = S0 + L;
@@ -396,11 +550,13 @@ int issue_beam(const DecodeCall& c, const BeamBufs& bb, hipStream_t s) {
   const vcap_gpt2_desc* d = c.d;
   const vcap_beam_params* bp = c.bp;
   const int E = d->n_embd, B = c.B, nb = bp->num_beams, L = bp->max_new_tokens, R = B * nb;
-  const int S0 = d->prefix_len + c.nids;
+  const Ragged* rg = c.rg;
+  const int S0 = rg ? rg->max_S0 : d->prefix_len + c.nids;   // ragged: the longest sequence's
   const DecState& w = bb.w;
   int nblk = bb.nblk;  // log_softmax partials per row the lm_head leaves (<= bb.nblk)
-  auto lm_head = [&](int S_new) -> int {
+  auto lm_head = [&](int S_new, const float* x = nullptr) -> int {
     RowsGemmArgs g = lm_head_args(d, w, R, S_new);
+    if (x) g.x = x;
     g.logits_raw = bb.logits; g.part_val = bb.part_max; g.part_sum = bb.part_sum; g.nblk = bb.nblk;
     g.max_blocks = bp->max_blocks;  // the streamed lm_head's grid (<= one workgroup per CU)
     nblk = bb.nblk;
@@ -409,18 +565,35 @@ int issue_beam(const DecodeCall& c, const BeamBufs& bb, hipStream_t s) {
   };
   VCAP_TRY(vcap_decode_init_dispatch(w.pt, R, w.maxp, w.finished, w.nbanned, s, w.skc, w.n_skc), "decode_init");
   // prefill: every beam row gets its sequence's prompt (HF expands the input to B * num_beams)
-  VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, c.prefix, d->prefix_len, c.ids, c.nids, d->wte, d->wpe, w.h, R, E, s,
-                                       0, nb),
-           "prefill_embed");
-  if (int rc = run_layers(d, w, R * S0, S0, 0, 0, s)) return rc;
-  if (int rc = lm_head(S0)) return rc;
+  if (rg) {
+    // the packed prefill: every beam row's own S0 rows; the lm_head over a copy of each one's last row
+    VCAP_TRY(vcap_prefill_embed_rows_dispatch(d->dtype, c.prefix, d->prefix_len, rg->ids(), rg->ids_off(),
+                                              rg->row_seq(), rg->row_pos(), d->wte, d->wpe, w.h, rg->M, E, nb, s),
+             "prefill_embed_rows");
+    if (int rc = run_layers(d, w, rg->M, 1, S0 - 1, 0, s, ragged_prefill_rows(*rg))) return rc;
+    VCAP_TRY(vcap_gather_rows_dispatch(w.h, rg->last_row(), rg->hl, R, E, s), "gather_last_rows");
+    if (int rc = lm_head(1, rg->hl)) return rc;
+  } else {
+    VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, c.prefix, d->prefix_len, c.ids, c.nids, d->wte, d->wpe, w.h, R, E,
+                                         s, 0, nb),
+             "prefill_embed");
+    if (int rc = run_layers(d, w, R * S0, S0, 0, 0, s)) return rc;
+    if (int rc = lm_head(S0)) return rc;
+  }
   VCAP_TRY(vcap_beam_init_dispatch(bb.st, B, nb, L, S0, bb.anc_ld, bp->eos_token_id, s), "beam_init");
   const LayerExtras anc{bb.st.anc, bb.anc_ld};
   for (int cur = 0; cur < L; ++cur) {
     if (cur > 0) {
       const int pos = S0 + cur - 1;
-      VCAP_TRY(vcap_embed_tokens_dispatch(d->dtype, bb.st.tok_next, R, d->wte, d->wpe, w.h, E, pos, s), "embed");
-      if (int rc = run_layers(d, w, R, 1, pos, bp->max_blocks, s, anc)) return rc;
+      if (rg) {
+        VCAP_TRY(vcap_embed_tokens_rows_dispatch(d->dtype, bb.st.tok_next, R, d->wte, d->wpe, w.h, E, rg->seq_len(),
+                                                 cur - 1, d->n_positions, s),
+                 "embed_rows");
+        if (int rc = run_layers(d, w, R, 1, pos, bp->max_blocks, s, ragged_step_rows(*rg, cur - 1, anc))) return rc;
+      } else {
+        VCAP_TRY(vcap_embed_tokens_dispatch(d->dtype, bb.st.tok_next, R, d->wte, d->wpe, w.h, E, pos, s), "embed");
+        if (int rc = run_layers(d, w, R, 1, pos, bp->max_blocks, s, anc)) return rc;
+      }
       if (int rc = lm_head(1)) return rc;
     }
     VCAP_TRY(vcap_beam_cand_dispatch(bb.st, bb.logits, bb.part_max, bb.part_sum, nblk, R, d->vocab, nb, L, cur,
@@ -428,7 +601,7 @@ int issue_beam(const DecodeCall& c, const BeamBufs& bb, hipStream_t s) {
                                      bp->eos_token_id, bb.chunks, s),
              "beam_cand");
     VCAP_TRY(vcap_beam_select_dispatch(bb.st, B, nb, L, d->vocab, bb.chunks, cur, bp->eos_token_id,
-                                       bp->length_penalty, S0, bb.anc_ld, s),
+                                       bp->length_penalty, S0, bb.anc_ld, s, rg ? rg->seq_len() : nullptr),
              "beam_select");
   }
   VCAP_TRY(vcap_beam_output_dispatch(bb.st, B, nb, L, c.out_ids, c.out_len, s), "beam_output");
@@ -536,6 +709,52 @@ int vcap_gpt2_sample(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const v
   if (int rc = check_prompt_rows(d, prompt_ids, prompt_len, B, gp->max_new_tokens)) return rc;
   DecodeCall c{d, prefix, prompt_ids, prompt_len, B, out_ids, gp, logits_out, sp, warped_out, force_ids};
   return run_decode(name, c, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+size_t vcap_gpt2_ragged_workspace_bytes(const vcap_gpt2_desc* d, const int* offsets, int B, int max_new_tokens) {
+  Ragged rg;
+  if (check_gpt2(d) || max_new_tokens <= 0 || max_new_tokens > 64 ||
+      ragged_shape("vcap_gpt2_ragged_workspace_bytes", d, offsets, B, max_new_tokens, 1, VCAP_E_UNSUPPORTED, &rg))
+    return 0;
+  return carved_bytes([&](Carver& c) {
+    carve_dec(c, d, B, rg.max_S0, max_new_tokens, rg.M);
+    carve_ragged(c, d, rg);
+  });
+}
+
+int vcap_gpt2_generate_ragged(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const float* prefix,
+                              const vcap_prompts* prompts, int B, int* out_ids, float* logits_out, void* workspace,
+                              size_t ws_bytes, void* stream) {
+  const char* name = "vcap_gpt2_generate_ragged";
+  if (int rc = check_gpt2_launch(d)) return rc;
+  if (!gp || !out_ids || !prefix || !prompts) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments");
+  if (gp->max_new_tokens <= 0) return fail(VCAP_E_ARG, "max_new_tokens must be > 0");
+  if (gp->max_new_tokens > 64)
+    return fail(VCAP_E_UNSUPPORTED, "max_new_tokens > 64 (the lm_head stages the processors' history in LDS)");
+  Ragged rg;
+  if (int rc = ragged_shape(name, d, prompts->offsets, B, gp->max_new_tokens, 1, VCAP_E_UNSUPPORTED, &rg)) return rc;
+  if (int rc = ragged_ids(name, d, prompts, rg)) return rc;
+  DecodeCall c{d, prefix, nullptr, 0, B, out_ids, gp, logits_out};
+  return run_decode_ragged(name, c, rg, prompts->ids, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+int vcap_gpt2_sample_ragged(const vcap_gpt2_desc* d, const vcap_gen_params* gp, const vcap_sample_params* sp,
+                            const float* prefix, const vcap_prompts* prompts, int B, int* out_ids, float* logits_out,
+                            float* warped_out, const int* force_ids, void* workspace, size_t ws_bytes, void* stream) {
+  const char* name = "vcap_gpt2_sample_ragged";
+  if (int rc = check_gpt2_launch(d)) return rc;
+  if (!gp || !sp || !out_ids || !prefix || !prompts) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments");
+  if (!(sp->temperature > 0.f) || !(sp->top_p > 0.0) || sp->top_p > 1.0 || sp->top_k < 1)
+    return fail(VCAP_E_ARG, std::string(name) + ": needs temperature > 0, 0 < top_p <= 1, top_k >= 1");
+  if (sp->top_k > vcap_sample_max_top_k() || d->vocab > 50 * 1024)
+    return fail(VCAP_E_UNSUPPORTED, std::string(name) + ": top_k <= 128 and vocab <= 51200");
+  if (gp->max_new_tokens <= 0 || gp->max_new_tokens > 64)
+    return fail(VCAP_E_UNSUPPORTED, "max_new_tokens must be in 1..64");
+  Ragged rg;
+  if (int rc = ragged_shape(name, d, prompts->offsets, B, gp->max_new_tokens, 1, VCAP_E_ARG, &rg)) return rc;
+  if (int rc = ragged_ids(name, d, prompts, rg)) return rc;
+  DecodeCall c{d, prefix, nullptr, 0, B, out_ids, gp, logits_out, sp, warped_out, force_ids};
+  return run_decode_ragged(name, c, rg, prompts->ids, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 size_t vcap_gpt2_beam_workspace_bytes(const vcap_gpt2_desc* d, int rows, int S0, int max_new_tokens) {
@@ -673,6 +892,59 @@ int vcap_gpt2_beam_search(const vcap_gpt2_desc* d, const vcap_beam_params* bp, c
   DecodeCall c{d, prefix, prompt_ids, prompt_len, B, out_ids};
   c.bp = bp;
   c.out_len = out_len;
+  if (!bp->use_graph) return issue_beam(c, bb, s);
+  return launch_cached(decode_key(c, workspace), s, [&](hipStream_t cs) { return issue_beam(c, bb, cs); });
+}
+
+// the ragged search's limits beyond ragged_shape's (the uniform search's, with the longest sequence's S0)
+static int check_beam_ragged(const vcap_gpt2_desc* d, int B, int nb, int L, const Ragged& rg) {
+  if (nb < 2 || nb > 8 || B > 8 || L <= 0 || L > 64 || rg.max_S0 + L > 128)
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gpt2_beam_search_ragged: needs 2 <= num_beams <= 8, B <= 8, max_new <= 64, "
+                                    "longest prefix + prompt + max_new <= 128");
+  if (nb * vcap_beam_chunks(d->vocab) * 2 * nb > 20 * 64)
+    return fail(VCAP_E_UNSUPPORTED, "num_beams too large for the vocabulary (candidate registers)");
+  return 0;
+}
+
+size_t vcap_gpt2_beam_search_ragged_workspace_bytes(const vcap_gpt2_desc* d, const int* offsets, int B, int num_beams,
+                                                    int max_new_tokens) {
+  const char* name = "vcap_gpt2_beam_search_ragged_workspace_bytes";
+  Ragged rg;
+  if (check_gpt2(d) || num_beams < 2 || num_beams > 8 || max_new_tokens <= 0 || max_new_tokens > 64 ||
+      ragged_shape(name, d, offsets, B, max_new_tokens, num_beams, VCAP_E_UNSUPPORTED, &rg) ||
+      check_beam_ragged(d, B, num_beams, max_new_tokens, rg))
+    return 0;
+  return carved_bytes([&](Carver& c) {
+    carve_beam(c, d, B, num_beams, rg.max_S0, max_new_tokens, rg.M);
+    carve_ragged(c, d, rg);
+  });
+}
+
+int vcap_gpt2_beam_search_ragged(const vcap_gpt2_desc* d, const vcap_beam_params* bp, const float* prefix,
+                                 const vcap_prompts* prompts, int B, int* out_ids, int* out_len, void* workspace,
+                                 size_t ws_bytes, void* stream) {
+  const char* name = "vcap_gpt2_beam_search_ragged";
+  if (int rc = check_gpt2_launch(d)) return rc;
+  if (!bp || !out_ids || !out_len || !prefix || !prompts) return fail(VCAP_E_ARG, std::string(name) + ": bad arguments");
+  const int nb = bp->num_beams, L = bp->max_new_tokens;
+  if (nb < 2 || nb > 8 || B > 8 || L <= 0 || L > 64)
+    return fail(VCAP_E_UNSUPPORTED, std::string(name) + ": needs 2 <= num_beams <= 8, B <= 8, max_new <= 64");
+  Ragged rg;
+  if (int rc = ragged_shape(name, d, prompts->offsets, B, L, nb, VCAP_E_UNSUPPORTED, &rg)) return rc;
+  if (int rc = check_beam_ragged(d, B, nb, L, rg)) return rc;
+  if (bp->early_stopping != 0) return fail(VCAP_E_UNSUPPORTED, "only early_stopping=False (the reference's presets)");
+  if (bp->max_blocks < 0) return fail(VCAP_E_ARG, std::string(name) + ": max_blocks < 0");
+  if (int rc = ragged_ids(name, d, prompts, rg)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Carver cv(workspace);
+  const BeamBufs bb = carve_beam(cv, d, B, nb, rg.max_S0, L, rg.M);
+  carve_ragged(cv, d, rg);
+  if (ws_bytes < cv.off) return fail(VCAP_E_WORKSPACE, std::string(name) + ": workspace too small");
+  if (int rc = upload_ragged(d, rg, prompts->ids, s)) return rc;
+  DecodeCall c{d, prefix, nullptr, 0, B, out_ids};
+  c.bp = bp;
+  c.out_len = out_len;
+  c.rg = &rg;
   if (!bp->use_graph) return issue_beam(c, bb, s);
   return launch_cached(decode_key(c, workspace), s, [&](hipStream_t cs) { return issue_beam(c, bb, cs); });
 }

@@ -30,7 +30,10 @@ enum { PRO_LN = 0, PRO_DIRECT = 1 };
 // EPI_LSE: raw logits -> logits_raw + per-workgroup (max, sum exp(x - max)) partials per row
 // (part_val / part_sum): the log_softmax statistics of beam search
 // EPI_STORE / EPI_RELU: T [M, ldo] = acc + bias / max(acc + bias, 0) (the text tower's in_proj and linear1)
-enum { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3, EPI_STORE = 4, EPI_LSE = 5, EPI_RELU = 6 };
+// EPI_QKV_ROWS: EPI_QKV with row m's (sequence, position) read from the row tables (ragged prompts):
+// seq = row_seq ? row_seq[m] : m, pos = row_pos[m] + pos_add; contiguous pages only
+enum { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3, EPI_STORE = 4, EPI_LSE = 5, EPI_RELU = 6,
+       EPI_QKV_ROWS = 7 };
 
 struct RowsGemmArgs {
   const void* x;  // PRO_LN: f32 residual rows; PRO_DIRECT: T rows
@@ -70,6 +73,10 @@ struct RowsGemmArgs {
   // arrival ticket sk_cnt (zeroed by vcap_decode_init at the start of every decode)
   float* sk_part;
   int* sk_cnt;
+  // EPI_QKV_ROWS: the row tables (device memory) in place of S_new / past
+  const int* row_seq;  // [M] or nullptr (row m is sequence m)
+  const int* row_pos;  // [M]
+  int pos_add;
 };
 
 // Exact-fp32 greedy token from a bf16 lm_head screen (f32 decoders; vcap_decode_finalize_dispatch):
@@ -168,6 +175,16 @@ struct DecodeKeys {
   // of that sequence (score -inf before the softmax); key 0 must be visible
   const uint8_t* kmask = nullptr;
   int mask_ld = 0;
+  // Ragged prompts: row m's query position from tables instead of (S_new, past) - sequence row_seq[m]
+  // (nullptr: m), position row_pos[m] + pos_add.  The dispatcher is then called with S_new = 1 and
+  // past + 1 = the longest sequence of the launch, min_len = the shortest; a sequence's length is
+  // seq_len[seq] with row_seq (a packed prefill), else the row's own context.  Sequences of <= 64 run the
+  // <= 64 form and longer ones the general form (what their one-prompt calls run).  No mask.
+  const int* row_seq = nullptr;
+  const int* row_pos = nullptr;
+  int pos_add = 0;
+  const int* seq_len = nullptr;
+  int min_len = 0;
 };
 hipError_t vcap_decode_attention_dispatch(int dt, const void* q, const void* kc, const void* vc, const DecodeKeys& keys,
                                           int maxp, void* out, int M, int H, int S_new, int past, hipStream_t s);
@@ -193,6 +210,13 @@ hipError_t vcap_score_combine_dispatch(const ScoreLmArgs& a, const uint8_t* kmas
 hipError_t vcap_prefill_embed_dispatch(int dt, const float* prefix, int P, const int* ids, int nids, const void* wte,
                                        const float* wpe, float* h, int B, int E, hipStream_t s, int pos0 = 0,
                                        int prefix_rep = 1);
+// Ragged prompts (device tables): rows row_seq[m] / row_pos[m] of a packed prefill; sequence r's prefix is
+// prefix[r / prefix_rep], its prompt ids[ids_off[r / prefix_rep] + (i - P)]
+hipError_t vcap_prefill_embed_rows_dispatch(int dt, const float* prefix, int P, const int* ids, const int* ids_off,
+                                            const int* row_seq, const int* row_pos, const void* wte, const float* wpe,
+                                            float* h, int M, int E, int prefix_rep, hipStream_t s);
+// dst[r] = src[rows[r]] (f32 rows of E): each sequence's last prefill row, for the lm_head
+hipError_t vcap_gather_rows_dispatch(const float* src, const int* rows, float* dst, int R, int E, hipStream_t s);
 hipError_t vcap_decode_init_dispatch(int* page_table, int B, int maxp, int* finished, int* nbanned, hipStream_t s,
                                      int* sk_cnt = nullptr, int n_sk = 0);
 hipError_t vcap_decode_finalize_dispatch(int dt, const float* part_val, const int* part_idx, int nblk, int B,
@@ -200,11 +224,21 @@ hipError_t vcap_decode_finalize_dispatch(int dt, const float* part_val, const in
                                          int ngram, int eos, int pad, int* out_ids, int out_ld, const void* wte,
                                          const float* wpe, float* h, int E, int pos_next, int vocab, hipStream_t s,
                                          const ScreenArgs* screen = nullptr);
+// Ragged prompts: the next input's position is min(seq_len[m] + pos_add, npos - 1) per row
+hipError_t vcap_decode_finalize_rows_dispatch(int dt, const float* part_val, const int* part_idx, int nblk, int B,
+                                              int step, int* finished, int* hist, int hist_ld, int* banned,
+                                              int* nbanned, int ngram, int eos, int pad, int* out_ids, int out_ld,
+                                              const void* wte, const float* wpe, float* h, int E, const int* seq_len,
+                                              int pos_add, int npos, int vocab, hipStream_t s,
+                                              const ScreenArgs* screen = nullptr);
 // The bf16 lm_head as the screen of an f32 greedy step (the stream kernel only: M <= 16); returns
 // hipErrorNotSupported, launching nothing, where that kernel does not apply.
 hipError_t vcap_lm_head_screen_dispatch(const RowsGemmArgs& a, int* nblk_out, int* tpb_out, hipStream_t s);
 hipError_t vcap_embed_tokens_dispatch(int dt, const int* tok, int rows, const void* wte, const float* wpe, float* h,
                                       int E, int pos, hipStream_t s);
+// ... at position min(seq_len[r] + pos_add, npos - 1) per row (ragged beam search)
+hipError_t vcap_embed_tokens_rows_dispatch(int dt, const int* tok, int rows, const void* wte, const float* wpe,
+                                           float* h, int E, const int* seq_len, int pos_add, int npos, hipStream_t s);
 // ---- device beam search (csrc/beam.hip) ----
 struct BeamState {  // per-call device state, carved from the caller's workspace (B batches, nb beams, L = max_new)
   int* run_seq;      // [B][nb][L] running hypotheses' tokens
@@ -227,7 +261,8 @@ hipError_t vcap_beam_cand_dispatch(const BeamState& st, const float* logits, con
                                    const float* part_sum, int nblk, int rows, int V, int nb, int L, int cur,
                                    float rep, int ngram, int min_new, int eos, int chunks, hipStream_t s);
 hipError_t vcap_beam_select_dispatch(const BeamState& st, int B, int nb, int L, int V, int chunks, int cur, int eos,
-                                     float length_penalty, int S0, int anc_ld, hipStream_t s);
+                                     float length_penalty, int S0, int anc_ld, hipStream_t s,
+                                     const int* seq_len = nullptr);  // seq_len [B * nb]: S0 of batch b = seq_len[b * nb]
 hipError_t vcap_beam_output_dispatch(const BeamState& st, int B, int nb, int L, int* out_ids, int* out_len,
                                      hipStream_t s);
 int vcap_beam_chunks(int V);

@@ -77,6 +77,11 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", C.c_double), ("seed", C.c_uint64)]
 
 
+class Prompts(C.Structure):
+    """vcap_prompts: host arrays; keep the ctypes arrays alive for the duration of the call."""
+    _fields_ = [("ids", C.POINTER(C.c_int)), ("offsets", C.POINTER(C.c_int))]
+
+
 class TextLayer(C.Structure):
     _fields_ = [("in_w", vp), ("in_b", vp), ("out_w", vp), ("out_b", vp), ("ln1_g", vp), ("ln1_b", vp),
                 ("fc1_w", vp), ("fc1_b", vp), ("fc2_w", vp), ("fc2_b", vp), ("ln2_g", vp), ("ln2_b", vp)]
@@ -156,6 +161,14 @@ SIGNATURES = {
     "vcap_ivf_search": (i32, [i32, vp, vp, vp, i64, vp, i32, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, i32, vp]),
     "vcap_text_workspace_bytes": (sz, [C.POINTER(TextDesc), i32, i32]),
     "vcap_text_encode": (i32, [C.POINTER(TextDesc), vp, i32, i32, vp, vp, vp, sz, vp]),
+    "vcap_gpt2_ragged_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(C.c_int), i32, i32]),
+    "vcap_gpt2_generate_ragged": (i32, [C.POINTER(GPT2Desc), C.POINTER(GenParams), vp, C.POINTER(Prompts), i32, vp,
+                                        vp, vp, sz, vp]),
+    "vcap_gpt2_sample_ragged": (i32, [C.POINTER(GPT2Desc), C.POINTER(GenParams), C.POINTER(SampleParams), vp,
+                                      C.POINTER(Prompts), i32, vp, vp, vp, vp, vp, sz, vp]),
+    "vcap_gpt2_beam_search_ragged_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(C.c_int), i32, i32, i32]),
+    "vcap_gpt2_beam_search_ragged": (i32, [C.POINTER(GPT2Desc), C.POINTER(BeamParams), vp, C.POINTER(Prompts), i32,
+                                           vp, vp, vp, sz, vp]),
     "vcap_probe_enable": (i32, [C.c_char_p, i32]),
     "vcap_probe_read": (i32, [C.c_char_p, fp, C.POINTER(C.c_int)]),
     "vcap_probe_read_launches": (i32, [C.c_char_p, fp, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]),

@@ -210,12 +210,18 @@ class HipTextDecoder:
                              eos=eos, seed=seed, use_graph=self.use_graph)
 
     @torch.no_grad()
-    def generate(self, video_emb: torch.Tensor, prompt: str = "", max_new_tokens: int = 32, num_beams: int = 1,
+    def generate(self, video_emb: torch.Tensor, prompt="", max_new_tokens: int = 32, num_beams: int = 1,
                  temperature: float = 1.0, top_p: float = 0.9, no_repeat_ngram_size: int = 3,
                  repetition_penalty: float = 1.15, min_new_tokens: int = 8) -> List[str]:
-        """GPT2TextDecoder.generate (text_decoder.py:105-146): video_emb [B,256] or [B,1,256]."""
-        prompt_ids = self.tokenizer.encode_prompt(prompt)
+        """GPT2TextDecoder.generate (text_decoder.py:105-146): video_emb [B,256] or [B,1,256]; `prompt` is
+        one string, or a list of B strings (one per video)."""
         prefix = self.prefix_embeds(video_emb)
+        if isinstance(prompt, str):
+            prompt_ids = self.tokenizer.encode_prompt(prompt)
+        else:   # one prompt per video: one ragged decode (row b = the one-prompt call's row)
+            if len(prompt) != prefix.shape[0]:
+                raise ValueError(f"{len(prompt)} prompts for {prefix.shape[0]} videos")
+            prompt_ids = [self.tokenizer.encode_prompt(p) for p in prompt]
         rows = self.generate_from_prefix(prefix, prompt_ids, max_new_tokens=max_new_tokens, num_beams=num_beams,
                                          temperature=temperature, top_p=top_p,
                                          no_repeat_ngram_size=no_repeat_ngram_size,
@@ -260,8 +266,9 @@ class HipVideoCaptionModel:
         return self.hip_encoder.encode(video.to(self.device), self._engine_prefix)
 
     @torch.no_grad()
-    def generate(self, video: torch.Tensor, prompt: str = "", **gen_kwargs) -> List[str]:
-        """VideoCaptionModel.generate (caption_model.py:93-101): encoder -> proj -> decoder.generate."""
+    def generate(self, video: torch.Tensor, prompt="", **gen_kwargs) -> List[str]:
+        """VideoCaptionModel.generate (caption_model.py:93-101): encoder -> proj -> decoder.generate.
+        `prompt`: one string for the batch, or a list with one string per video."""
         emb = self.proj(self.encoder(video.to(self.device)))
         return self.decoder.generate(emb, prompt=prompt, **gen_kwargs)
 

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -254,6 +254,36 @@ class ScoreResult:
         return None if self.nll_sum is None else self.nll_sum / self.count
 
 
+def split_prompts(prompt_ids, B: int, merge_equal: bool = True) -> Tuple[List[int], Optional[List[List[int]]]]:
+    """What a decode call's `prompt_ids` means: (ids, None) for one prompt shared by the B rows - a flat
+    sequence of ids, or B equal sequences - else (all ids concatenated, the B per-row id lists): ragged.
+    merge_equal=False keeps B equal sequences ragged (HipGPT2Decoder.force_ragged)."""
+    items = list(prompt_ids)
+    if not any(isinstance(x, (list, tuple, np.ndarray, torch.Tensor)) for x in items):
+        return [int(i) for i in items], None
+    rows = []
+    for x in items:
+        if not isinstance(x, (list, tuple, np.ndarray, torch.Tensor)):
+            raise ValueError("prompt_ids mixes ids and sequences: give one flat prompt or one sequence per row")
+        rows.append([int(i) for i in (x.tolist() if hasattr(x, "tolist") else x)])
+    if len(rows) != B:
+        raise ValueError(f"prompt_ids has {len(rows)} prompts for {B} rows")
+    if merge_equal and all(r == rows[0] for r in rows):
+        return rows[0], None
+    return [i for r in rows for i in r], rows
+
+
+def _prompts_arg(rows: List[List[int]]):
+    """vcap_prompts of per-row id lists + the ctypes arrays it points into (keep them for the call)."""
+    flat = [i for r in rows for i in r]
+    offs = [0]
+    for r in rows:
+        offs.append(offs[-1] + len(r))
+    ids_arr = (C.c_int * max(len(flat), 1))(*flat)
+    off_arr = (C.c_int * len(offs))(*offs)
+    return N.Prompts(ids=ids_arr, offsets=off_arr), ids_arr, off_arr
+
+
 class HipGPT2Decoder:
     """GPT2LMHeadModel greedy generate from inputs_embeds (text_decoder.py:131-144) on the HIP path."""
 
@@ -267,6 +297,9 @@ class HipGPT2Decoder:
     # which counted 2^-8 for BOTH roundings; tests/test_gpu_lm_screen.py builds a near-tie that the
     # old constant gets wrong and this one does not.
     SCREEN_C = 0.0082
+    # True: per-row prompts go through the _ragged entry points even when they are all equal (or B = 1);
+    # by default equal prompts take the one-prompt call.  For tests and A/B measurements.
+    force_ragged = False
 
     def __init__(self, sd: Dict[str, np.ndarray], arch: GPT2Arch, precision: str = "bf16", device="cuda",
                  prefix_len: int = 4, screen: bool = True):
@@ -341,12 +374,24 @@ class HipGPT2Decoder:
     def workspace_bytes(self, B: int, prompt_len: int, max_new: int) -> int:
         return int(N.lib().vcap_gpt2_workspace_bytes(C.byref(self.desc), B, self.prefix_len + prompt_len, max_new))
 
-    def generate_ids(self, prefix: torch.Tensor, prompt_ids: Sequence[int], cfg: GenConfig,
+    def ragged_workspace_bytes(self, rows: List[List[int]], max_new: int, num_beams: int = 1) -> int:
+        """Workspace of a ragged call (0: the device refuses the shape - see include/vcap.h)."""
+        _, _, off = _prompts_arg(rows)
+        if num_beams > 1:
+            return int(N.lib().vcap_gpt2_beam_search_ragged_workspace_bytes(C.byref(self.desc), off, len(rows),
+                                                                            int(num_beams), int(max_new)))
+        return int(N.lib().vcap_gpt2_ragged_workspace_bytes(C.byref(self.desc), off, len(rows), int(max_new)))
+
+    def generate_ids(self, prefix: torch.Tensor, prompt_ids: Sequence, cfg: GenConfig,
                      out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
                      workspace: Optional["_Workspace"] = None, lengths_out: Optional[torch.Tensor] = None,
                      warped_out: Optional[torch.Tensor] = None, force_ids: Optional[torch.Tensor] = None
                      ) -> torch.Tensor:
         """prefix [B,P,E] f32 device, prompt ids (BOS-only prompt = [eos]) -> int32 [B, max_new] EOS-padded.
+
+        `prompt_ids` is one flat sequence of ids for the whole batch, or B sequences, one per row (ragged
+        prompts: row b gives what a B = 1 call with prefix row b and prompt b gives).  B equal sequences
+        take the one-prompt path.
 
         `workspace` (KV pages + decode scratch) defaults to the decoder's own; concurrent decodes on
         different streams pass one each (the captured graph is keyed on it).  cfg.num_beams > 1 runs
@@ -358,7 +403,7 @@ class HipGPT2Decoder:
         if P != self.prefix_len or E != self.arch.n_embd:
             raise ValueError(f"prefix shape {tuple(prefix.shape)} != [B,{self.prefix_len},{self.arch.n_embd}]")
         prefix = prefix.to(torch.float32).contiguous()
-        ids = list(int(i) for i in prompt_ids)
+        ids, rows = split_prompts(prompt_ids, B, not self.force_ragged)
         mx = int(cfg.max_new_tokens)
         fresh = (out is None and logits_out is None and workspace is None and warped_out is None and force_ids is None
                  and cfg.use_graph)
@@ -372,7 +417,7 @@ class HipGPT2Decoder:
                                      torch.empty(B, mx, dtype=torch.int32, device=self.device))
             sp, so = self._stable[key]
             sp.copy_(prefix)
-            self.generate_ids(sp, ids, cfg, out=so)
+            self.generate_ids(sp, ids if rows is None else rows, cfg, out=so)
             return so.clone()
         if out is None:
             out = torch.empty(B, mx, dtype=torch.int32, device=prefix.device)
@@ -386,7 +431,15 @@ class HipGPT2Decoder:
                          pad_token_id=int(cfg.pad_token_id), use_graph=int(bool(cfg.use_graph)),
                          max_blocks=int(cfg.max_blocks))
         arr = (C.c_int * max(len(ids), 1))(*ids)
-        ws = (workspace or self.ws).get(self.workspace_bytes(B, len(ids), mx))
+        if rows is not None:
+            nbytes = self.ragged_workspace_bytes(rows, mx)
+            if nbytes == 0:
+                raise N.VcapError("vcap_gpt2_ragged_workspace_bytes: unsupported shape (prompts over 64 ids, more "
+                                  "rows than vcap_gpt2_max_rows(), or a context past n_positions)", N.E_UNSUPPORTED)
+            ws = (workspace or self.ws).get(nbytes)
+            pr, _ids_keep, _off_keep = _prompts_arg(rows)
+        else:
+            ws = (workspace or self.ws).get(self.workspace_bytes(B, len(ids), mx))
         if cfg.do_sample:
             if warped_out is not None and (tuple(warped_out.shape) != (mx, B, self.arch.vocab)
                                            or warped_out.dtype != torch.float32 or not warped_out.is_contiguous()):
@@ -397,10 +450,22 @@ class HipGPT2Decoder:
                 force_ids = force_ids.to(device=prefix.device, dtype=torch.int32).contiguous()
             sp = N.SampleParams(temperature=float(cfg.temperature), top_k=int(cfg.top_k), top_p=float(cfg.top_p),
                                 seed=int(cfg.seed) & 0xFFFFFFFFFFFFFFFF)
+            if rows is not None:
+                N.check(N.lib().vcap_gpt2_sample_ragged(C.byref(self.desc), C.byref(gp), C.byref(sp),
+                                                        prefix.data_ptr(), C.byref(pr), B, out.data_ptr(),
+                                                        N.ptr(logits_out), N.ptr(warped_out), N.ptr(force_ids),
+                                                        ws.data_ptr(), ws.numel(), _stream(prefix.device)),
+                        "vcap_gpt2_sample_ragged")
+                return out
             N.check(N.lib().vcap_gpt2_sample(C.byref(self.desc), C.byref(gp), C.byref(sp), prefix.data_ptr(), arr,
                                              len(ids), B, out.data_ptr(), N.ptr(logits_out), N.ptr(warped_out),
                                              N.ptr(force_ids), ws.data_ptr(), ws.numel(), _stream(prefix.device)),
                     "vcap_gpt2_sample")
+            return out
+        if rows is not None:
+            N.check(N.lib().vcap_gpt2_generate_ragged(C.byref(self.desc), C.byref(gp), prefix.data_ptr(), C.byref(pr),
+                                                      B, out.data_ptr(), N.ptr(logits_out), ws.data_ptr(), ws.numel(),
+                                                      _stream(prefix.device)), "vcap_gpt2_generate_ragged")
             return out
         N.check(N.lib().vcap_gpt2_generate(C.byref(self.desc), C.byref(gp), prefix.data_ptr(), arr, len(ids), B,
                                            out.data_ptr(), N.ptr(logits_out), ws.data_ptr(), ws.numel(),
@@ -471,14 +536,21 @@ class HipGPT2Decoder:
         B, P, E = prefix.shape
         if P != self.prefix_len or E != self.arch.n_embd:
             raise ValueError(f"prefix shape {tuple(prefix.shape)} != [B,{self.prefix_len},{self.arch.n_embd}]")
-        ids = [int(i) for i in prompt_ids]
+        ids, rows = split_prompts(prompt_ids, B, not self.force_ragged)
         mx = int(cfg.max_new_tokens)
         prefix = prefix.to(torch.float32).contiguous()
         out = out if out is not None else torch.empty(B, mx, dtype=torch.int32, device=prefix.device)
         if lengths_out is None:
             lengths_out = torch.empty(B, dtype=torch.int32, device=prefix.device)
         S0 = self.prefix_len + len(ids)
-        nbytes = int(N.lib().vcap_gpt2_beam_search_workspace_bytes(C.byref(self.desc), B, int(cfg.num_beams), S0, mx))
+        if rows is not None:
+            nbytes = self.ragged_workspace_bytes(rows, mx, int(cfg.num_beams))
+        else:
+            nbytes = int(N.lib().vcap_gpt2_beam_search_workspace_bytes(C.byref(self.desc), B, int(cfg.num_beams), S0,
+                                                                       mx))
+        if nbytes == 0 and rows is not None:
+            raise N.VcapError("vcap_gpt2_beam_search_ragged_workspace_bytes: unsupported shape (B > 8, num_beams "
+                              "outside 2..8, too many prefill rows, or a context past 128)", N.E_UNSUPPORTED)
         if nbytes == 0:
             raise ValueError("vcap_gpt2_beam_search_workspace_bytes: unsupported shape")
         ws = (workspace or self.ws).get(nbytes)
@@ -487,6 +559,13 @@ class HipGPT2Decoder:
                           repetition_penalty=float(cfg.repetition_penalty), length_penalty=float(cfg.length_penalty),
                           early_stopping=0, eos_token_id=int(cfg.eos_token_id), use_graph=int(bool(cfg.use_graph)),
                           max_blocks=int(cfg.max_blocks))
+        if rows is not None:
+            pr, _ids_keep, _off_keep = _prompts_arg(rows)
+            N.check(N.lib().vcap_gpt2_beam_search_ragged(C.byref(self.desc), C.byref(bp), prefix.data_ptr(),
+                                                         C.byref(pr), B, out.data_ptr(), lengths_out.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), _stream(prefix.device)),
+                    "vcap_gpt2_beam_search_ragged")
+            return out
         arr = (C.c_int * max(len(ids), 1))(*ids)
         N.check(N.lib().vcap_gpt2_beam_search(C.byref(self.desc), C.byref(bp), prefix.data_ptr(), arr, len(ids), B,
                                               out.data_ptr(), lengths_out.data_ptr(), ws.data_ptr(), ws.numel(),

@@ -97,15 +97,41 @@ def beam_search_any(dec, prefix: torch.Tensor, prompt_ids: Sequence[int], *, num
     the device search refuses (num_beams > 8 or too many candidates for the vocabulary, context
     > 128) runs the host-bookkeeping search over the same step kernels.  Sequences are independent
     in HF's search, so chunking changes nothing but the padding: rows are EOS-padded to the longest
-    hypothesis of the whole batch, as one generate() call returns them."""
+    hypothesis of the whole batch, as one generate() call returns them.  `prompt_ids` may be one
+    sequence per row (ragged prompts; B equal ones are the one-prompt call)."""
+    from .model import split_prompts
     B = prefix.shape[0]
-    S0 = dec.prefix_len + len(prompt_ids)
+    prompt_ids, per_row = split_prompts(prompt_ids, B)
     limit = int(N.lib().vcap_gpt2_max_rows())
-    step = max(1, min(BEAM_DEVICE_MAX_B, limit // max(1, num_beams * S0)))
     kw = dict(num_beams=num_beams, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens,
               no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, eos=eos,
               length_penalty=length_penalty)
     rows: List[List[int]] = []
+    if per_row is not None:
+        # ragged prompts: chunks within the ragged search's limits (<= 8 sequences, num_beams * sum of
+        # (prefix + prompt) <= vcap_gpt2_max_rows()); a chunk the device refuses (a context past 128, ...)
+        # runs the host search one row at a time, each with its own prompt
+        i = 0
+        while i < B:
+            j, used = i, 0
+            while j < B and j - i < BEAM_DEVICE_MAX_B:
+                need = num_beams * (dec.prefix_len + len(per_row[j]))
+                if j > i and used + need > limit:
+                    break
+                used += need
+                j += 1
+            try:
+                rows += beam_search_device(dec, prefix[i:j], per_row[i:j], use_graph=use_graph, **kw)
+            except N.VcapError as e:
+                if e.rc != N.E_UNSUPPORTED:
+                    raise
+                for r in range(i, j):
+                    rows += beam_search(dec, prefix[r:r + 1], per_row[r], **kw)
+            i = j
+        width = max(len(r) for r in rows)
+        return [r + [eos] * (width - len(r)) for r in rows]
+    S0 = dec.prefix_len + len(prompt_ids)
+    step = max(1, min(BEAM_DEVICE_MAX_B, limit // max(1, num_beams * S0)))
     device_ok = True
     for i in range(0, B, step):
         chunk = prefix[i:i + step]
