@@ -414,6 +414,69 @@ int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, 
                     const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
                     size_t ws_bytes, void* stream);
 
+/* ---- the scoring call's gradient w.r.t. inputs_embeds (added within ABI v16: new symbols and two new structs,
+ *      nothing existing changes): vcap_gpt2_score's forward, then an activation-only backward through the
+ *      frozen GPT-2 - what fitting a prefix mapper, soft prompts or an embedding saliency needs (the
+ *      reference's recipe: src/cli/train_caption_mapper.py compute_loss_local, GPT-2 and ViT frozen).  No
+ *      weight gradients exist on the device.
+ *        embeds, key_mask, targets, logprob_out, loss_out: exactly vcap_gpt2_score's, the precondition
+ *                    key_mask[b][0] != 0 included; targets is required here
+ *        grad_logprob [B, S] f32 or NULL: the weight w[b][i] of each counted position's log-prob lp[b][i];
+ *                    NULL = -1 everywhere (the gradient of loss_out[0], the NLL sum).  Entries at ignored
+ *                    positions are not read.
+ *        grad_embeds [B, S, E] f32, required: sum over the counted (b, i) of w[b][i] * d lp[b][i] / d embeds.
+ *                    wpe is added to the embeddings, so the gradient passes through it unchanged.  Every
+ *                    entry of a sequence that breaks the mask precondition is NaN.
+ *      The grad desc carries the extra weight copies the backward reads, all in the decoder dtype and plain
+ *      row-major: HF's Conv1D [in, out] matrices as stored (every dx = dy . W^T is then an ordinary
+ *      C[m][n] = sum_k A[m][k] W[n][k] product), the Linear-layout [out, in] copies of c_attn and c_fc for
+ *      the recompute of q | k | v and of the pre-GELU c_fc output, and wte transposed with its vocabulary
+ *      axis zero-padded to a multiple of 128.
+ *      Limits and codes are vcap_gpt2_score's, refused before any launch: B * S <= vcap_gpt2_max_rows(),
+ *      S <= n_positions (VCAP_E_UNSUPPORTED); both decoder dtypes; a grad desc whose dtype / n_embd /
+ *      n_layer differ from the decoder's or whose vocab_pad is not the padded vocabulary, null pointers and
+ *      bad sizes: VCAP_E_ARG; a small workspace: VCAP_E_WORKSPACE (the query returns 0 outside the limits).
+ *      Not graph-captured; leaves no KV state.
+ *      Contracts:
+ *        - logprob_out and loss_out are bit-identical to vcap_gpt2_score's: the forward is that schedule,
+ *          with copies of the f32 residual stream (each layer's input, after each attention c_proj, the last
+ *          layer's output) taken between its launches.
+ *        - Deterministic: fixed reduction orders and no float atomics; two calls give the same bits.
+ *        - Batch-independent: the bits of sequence b's gradient depend on its own embeds, mask, targets and
+ *          weights, S and the model only - not on B nor on the other sequences.  Every product runs one
+ *          128x128-tile kernel at every row count (vcap_set_gemm_policy is not followed); its K range is cut
+ *          into slabs of a constant width (256 columns in the block products, 2048 in the K = vocab product
+ *          of the lm_head), a function of the model's shape alone, summed in slab order.
+ *        - Exact zeros: the gradient is exactly +0 at a position after its sequence's last counted
+ *          position, everywhere in a sequence with no counted position, and at a hidden key whose own
+ *          target is ignored.
+ *      Rounding points with a bf16 decoder (an f32 decoder rounds nowhere): every MFMA operand is bf16 (RNE) -
+ *      the recomputed LayerNorm rows, dlogit = w (onehot - softmax), the residual gradient where it enters
+ *      the two c_proj^T products, du = dact * gelu_new'(u), dq | dk | dv - and the recomputed q | k | v are
+ *      rounded to bf16 values as the forward stores them.  Accumulation, the residual gradient stream and
+ *      the softmax / LayerNorm / GELU backward arithmetic are f32; the attention backward is f32 throughout. ---- */
+typedef struct vcap_gpt2_grad_layer {
+  const void* attn_c;        /* [E, 3E]  c_attn Conv1D as stored */
+  const void* aproj_c;       /* [E, E]   attn c_proj */
+  const void* fc_c;          /* [E, 4E]  mlp c_fc */
+  const void* mproj_c;       /* [4E, E]  mlp c_proj */
+  const void* attn_l;        /* [3E, E]  c_attn transposed (Linear layout) */
+  const void* fc_l;          /* [4E, E]  c_fc transposed */
+} vcap_gpt2_grad_layer;
+
+typedef struct vcap_gpt2_grad_desc {
+  int dtype, n_embd, n_layer;  /* the decoder's */
+  int vocab_pad;               /* vocab rounded up to a multiple of 128 */
+  const void* wte_t;           /* [E, vocab_pad]: wte transposed, columns >= vocab zero */
+  const vcap_gpt2_grad_layer* layers;  /* host array of n_layer entries */
+} vcap_gpt2_grad_desc;
+
+size_t vcap_gpt2_score_backward_workspace_bytes(const vcap_gpt2_desc* d, const vcap_gpt2_grad_desc* g, int B, int S);
+int vcap_gpt2_score_backward(const vcap_gpt2_desc* d, const vcap_gpt2_grad_desc* g, const float* embeds, int B, int S,
+                             const uint8_t* key_mask, const int* targets, const float* grad_logprob,
+                             float* grad_embeds, float* logprob_out, float* loss_out, void* workspace,
+                             size_t ws_bytes, void* stream);
+
 /* ---- video retrieval (added within ABI v16: new symbols only, no struct changes): the inference half of
  *      the reference's second product - embed a clip, search a flat inner-product index of clip
  *      embeddings.  Reference interfaces: ViTTextAlignModel.encode_video

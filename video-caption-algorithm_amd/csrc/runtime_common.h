@@ -66,6 +66,18 @@ struct ProbeScope {
   ~ProbeScope();
 };
 
+// ---- runtime_gpt2.hip, for the scoring call's backward (runtime_gpt2_grad.hip)
+// the descriptor checks of every GPT-2 entry point (launch: plus the weight pointers a launch dereferences)
+int vcap_gpt2_check_desc(const vcap_gpt2_desc* d, bool launch);
+struct ScoreForward {   // what the forward leaves in its workspace for the backward
+  const float* pmax;    // [B*S][nparts] per 64-column part: max and sum exp(x - max) of the row's logits
+  const float* psum;
+  int nparts;
+};
+int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
+                       const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
+                       float* snap, hipStream_t s, ScoreForward* out);
+
 // ---- graph_cache.hip
 // Bytes of everything a captured decode bakes in; two calls replay one graph only if their keys are equal.
 struct GraphKey {

@@ -138,6 +138,10 @@ struct LayerExtras {
   int pos_add = 0;
   const int* seq_len = nullptr;   // [seqs], with row_seq
   int min_len = 0;                // the shortest sequence of the launch (past + 1 is the longest)
+  // the scoring call's backward (host only: copies between the launches, which stay as they are): the f32
+  // residual stream [M, E] is copied to snap + 2 l * M * E at layer l's input, to snap + (2 l + 1) * M * E
+  // after its attention c_proj and to snap + 2 L * M * E at the last layer's output
+  float* snap = nullptr;
 };
 
 int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int past, int max_blocks, hipStream_t s,
@@ -145,8 +149,11 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
   const int E = d->n_embd, H = d->n_head, L = d->n_layer;
   const int dt = d->dtype;
   const size_t es = esize(dt);
+  const size_t snap_n = (size_t)M * E;
   for (int l = 0; l < L; ++l) {
     const vcap_gpt2_layer& ly = d->layers[l];
+    if (x.snap)
+      VCAP_TRY(hipMemcpyAsync(x.snap + 2 * l * snap_n, w.h, snap_n * 4, hipMemcpyDeviceToDevice, s), "snapshot");
     RowsGemmArgs a{};
     a.M = M;
     a.ln_eps = d->ln_eps;
@@ -174,6 +181,8 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
     b.M = M; b.x = w.attn; b.ldx = E; b.w = ly.aproj_w; b.bias = ly.aproj_b; b.N = E; b.K = E;
     b.out = w.h; b.ldo = E; b.max_blocks = max_blocks;
     VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_DIRECT, EPI_RESID, b, nullptr, s), "attn_c_proj");
+    if (x.snap)
+      VCAP_TRY(hipMemcpyAsync(x.snap + (2 * l + 1) * snap_n, w.h, snap_n * 4, hipMemcpyDeviceToDevice, s), "snapshot");
     // 4) ln_2 + c_fc + gelu_new
     RowsGemmArgs c{};
     c.M = M; c.x = w.h; c.ldx = E; c.ln_g = ly.ln2_g; c.ln_b = ly.ln2_b; c.ln_eps = d->ln_eps;
@@ -187,6 +196,8 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
     e.sk_part = w.skp; e.sk_cnt = w.skc;
     VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_DIRECT, EPI_RESID, e, nullptr, s), "mlp_c_proj");
   }
+  if (x.snap)
+    VCAP_TRY(hipMemcpyAsync(x.snap + 2 * L * snap_n, w.h, snap_n * 4, hipMemcpyDeviceToDevice, s), "snapshot");
   return 0;
 }
 
@@ -635,6 +646,32 @@ ScoreBufs carve_score(Carver& c, const vcap_gpt2_desc* d, int B, int S) {
 
 }  // namespace
 
+int vcap_gpt2_check_desc(const vcap_gpt2_desc* d, bool launch) { return launch ? check_gpt2_launch(d) : check_gpt2(d); }
+
+// vcap_gpt2_score's schedule (arguments checked by the caller; workspace of vcap_gpt2_score_workspace_bytes).
+// snap / out: the backward's residual-stream snapshots (LayerExtras.snap) and the buffers it reads afterwards.
+int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
+                       const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
+                       float* snap, hipStream_t s, ScoreForward* out) {
+  Carver c(workspace);
+  const ScoreBufs b = carve_score(c, d, B, S);
+  const DecState& w = b.w;
+  const int M = B * S, E = d->n_embd;
+  VCAP_TRY(vcap_decode_init_dispatch(w.pt, B, w.maxp, w.finished, w.nbanned, s, w.skc, w.n_skc), "decode_init");
+  // the prefill-embedding kernel with every position taken from `embeds`: h = embeds + wpe[0..S)
+  VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, embeds, S, nullptr, 0, d->wte, d->wpe, w.h, B, E, s), "embed_inputs");
+  LayerExtras x{nullptr, 0, key_mask, S};
+  x.snap = snap;
+  if (int rc = run_layers(d, w, M, S, 0, 0, s, x)) return rc;
+  VCAP_TRY(vcap_layernorm_dispatch(d->dtype, w.h, E, b.xn, E, d->lnf_g, d->lnf_b, M, E, d->ln_eps, s), "ln_f");
+  ScoreLmArgs a{b.xn, d->wte, M, d->vocab, E, targets, logits_out, b.pmax, b.psum, b.tlogit, b.nparts};
+  VCAP_TRY(vcap_score_lm_dispatch(d->dtype, a, s), "score_lm_head");
+  if (targets)
+    VCAP_TRY(vcap_score_combine_dispatch(a, key_mask, S, b.logprob, logprob_out, loss_out, s), "score_combine");
+  if (out) *out = ScoreForward{b.pmax, b.psum, b.nparts};
+  return 0;
+}
+
 // =====================================================================================================
 extern "C" {
 
@@ -845,21 +882,8 @@ int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, 
   if (S > d->n_positions) return fail(VCAP_E_UNSUPPORTED, "S exceeds n_positions");
   if (ws_bytes < vcap_gpt2_score_workspace_bytes(d, B, S))
     return fail(VCAP_E_WORKSPACE, "vcap_gpt2_score: workspace too small (vcap_gpt2_score_workspace_bytes)");
-  hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace);
-  const ScoreBufs b = carve_score(c, d, B, S);
-  const DecState& w = b.w;
-  const int M = B * S, E = d->n_embd;
-  VCAP_TRY(vcap_decode_init_dispatch(w.pt, B, w.maxp, w.finished, w.nbanned, s, w.skc, w.n_skc), "decode_init");
-  // the prefill-embedding kernel with every position taken from `embeds`: h = embeds + wpe[0..S)
-  VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, embeds, S, nullptr, 0, d->wte, d->wpe, w.h, B, E, s), "embed_inputs");
-  if (int rc = run_layers(d, w, M, S, 0, 0, s, LayerExtras{nullptr, 0, key_mask, S})) return rc;
-  VCAP_TRY(vcap_layernorm_dispatch(d->dtype, w.h, E, b.xn, E, d->lnf_g, d->lnf_b, M, E, d->ln_eps, s), "ln_f");
-  ScoreLmArgs a{b.xn, d->wte, M, d->vocab, E, targets, logits_out, b.pmax, b.psum, b.tlogit, b.nparts};
-  VCAP_TRY(vcap_score_lm_dispatch(d->dtype, a, s), "score_lm_head");
-  if (targets)
-    VCAP_TRY(vcap_score_combine_dispatch(a, key_mask, S, b.logprob, logprob_out, loss_out, s), "score_combine");
-  return 0;
+  return vcap_score_forward(d, embeds, B, S, key_mask, targets, logits_out, logprob_out, loss_out, workspace, nullptr,
+                            (hipStream_t)stream, nullptr);
 }
 
 size_t vcap_gpt2_beam_search_workspace_bytes(const vcap_gpt2_desc* d, int B, int num_beams, int S0,

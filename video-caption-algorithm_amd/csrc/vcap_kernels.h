@@ -207,6 +207,32 @@ hipError_t vcap_score_lm_dispatch(int dt, const ScoreLmArgs& a, hipStream_t s);
 // loss_out = {sum of -logprob over the counted rows in row order, their count}
 hipError_t vcap_score_combine_dispatch(const ScoreLmArgs& a, const uint8_t* kmask, int S, float* logprob_ws,
                                        float* logprob_out, float* loss_out, hipStream_t s);
+// ---- the scoring call's backward (csrc/score_backward.hip): activation gradients, decoder dtype dt ----
+// C f32 [M, ldc] = A [M, K] . W [N, K]^T with the 128x128 tile kernel at every M; N % 128 == 0, K a multiple of
+// the K step.  k_per_slab > 0: K range z of that many columns goes to the slab C + z * M * ldc
+// (ceil(K / k_per_slab) slabs).  vcap_grad_slab_sum_dispatch: out [n] = the slabs added in slab order, then
+// + bias [N] (rows of N columns) and, round_bf16, rounded to bf16 values.
+hipError_t vcap_grad_gemm_dispatch(int dt, const void* A, long lda, const void* W, long ldw, float* C, long ldc,
+                                   int M, int N, int K, int k_per_slab, hipStream_t s);
+hipError_t vcap_grad_slab_sum_dispatch(const float* slabs, long n, int nslab, const float* bias, int N,
+                                       int round_bf16, float* out, hipStream_t s);
+// lse [M] from the score kernel's parts, then dl [M, Vpad] (dt) = w (1[v == target] - exp(logit - lse)); w == nullptr
+// is -1; rows whose target is ignored and columns >= V are +0
+hipError_t vcap_score_dlogit_dispatch(int dt, const float* part_max, const float* part_sum, int nparts,
+                                      const float* logits, const int* targets, const float* w, int M, int V, int Vpad,
+                                      float* lse, void* dl, hipStream_t s);
+// g [M, E] += the LayerNorm input gradient of dy at the rows x (gamma frozen)
+hipError_t vcap_ln_backward_dispatch(const float* x, const float* dy, const float* gamma, float eps, int M, int E,
+                                     float* g, hipStream_t s);
+hipError_t vcap_gelu_backward_dispatch(int dt, const float* u, const float* dact, long n, void* du, hipStream_t s);
+hipError_t vcap_grad_to_bf16_dispatch(const float* x, long n, void* y, hipStream_t s);
+// qkv [B*S, 3 * 64 H] f32, dO [B*S, 64 H] f32, kmask [B, S] or nullptr; P, dS: [B*H, S, S] f32 scratch;
+// dqkv [B*S, 3 * 64 H] (dt).  S <= 512.
+hipError_t vcap_attn_backward_dispatch(int dt, const float* qkv, const float* dO, const uint8_t* kmask, int B, int S,
+                                       int H, float* P, float* dS, void* dqkv, hipStream_t s);
+// out = g + 0; NaN for the rows of a sequence with kmask[seq][0] == 0
+hipError_t vcap_grad_finish_dispatch(const float* g, const uint8_t* kmask, int B, int S, int E, float* out,
+                                     hipStream_t s);
 hipError_t vcap_prefill_embed_dispatch(int dt, const float* prefix, int P, const int* ids, int nids, const void* wte,
                                        const float* wpe, float* h, int B, int E, hipStream_t s, int pos0 = 0,
                                        int prefix_rep = 1);

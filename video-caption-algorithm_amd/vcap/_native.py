@@ -61,6 +61,15 @@ class GPT2Desc(C.Structure):
                 ("screen_bound", f32)]
 
 
+class GPT2GradLayer(C.Structure):
+    _fields_ = [("attn_c", vp), ("aproj_c", vp), ("fc_c", vp), ("mproj_c", vp), ("attn_l", vp), ("fc_l", vp)]
+
+
+class GPT2GradDesc(C.Structure):
+    _fields_ = [("dtype", i32), ("n_embd", i32), ("n_layer", i32), ("vocab_pad", i32), ("wte_t", vp),
+                ("layers", C.POINTER(GPT2GradLayer))]
+
+
 class GenParams(C.Structure):
     _fields_ = [("max_new_tokens", i32), ("min_new_tokens", i32), ("no_repeat_ngram_size", i32),
                 ("repetition_penalty", f32), ("eos_token_id", i32), ("pad_token_id", i32), ("use_graph", i32),
@@ -146,6 +155,9 @@ SIGNATURES = {
     "vcap_gpt2_forward_embeds": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "vcap_gpt2_score_workspace_bytes": (sz, [C.POINTER(GPT2Desc), i32, i32]),
     "vcap_gpt2_score": (i32, [C.POINTER(GPT2Desc), vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "vcap_gpt2_score_backward_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), i32, i32]),
+    "vcap_gpt2_score_backward": (i32, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), vp, i32, i32, vp, vp, vp, vp, vp,
+                                       vp, vp, sz, vp]),
     "vcap_l2_normalize": (i32, [vp, i64, vp, i64, i32, i32, f32, i32, vp]),
     "vcap_ip_index_convert": (i32, [vp, i64, i32, i32, i32, vp, vp]),
     "vcap_ip_search_workspace_bytes": (sz, [i64, i32, i32, i32]),

@@ -151,12 +151,11 @@ class HipTextDecoder:
         """wte rows [.., E] f32 of the decoder's own table: the rows its generate() feeds back."""
         return self.hip.wte[ids.to(self.hip.device).long()].float()
 
-    @torch.no_grad()
-    def forward_from_prefix(self, prefix: torch.Tensor, input_ids: torch.Tensor,
-                            attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
-                            want_logits: bool = True):
-        """GPT2TextDecoder.forward after the mapper: prefix [B, P, E] -> vcap.model.ScoreResult over the
-        P + L positions (one vcap_gpt2_score pass per chunk of sequences)."""
+    def score_inputs(self, prefix: torch.Tensor, input_ids: torch.Tensor,
+                     attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+        """What GPT2TextDecoder.forward feeds GPT-2 after the mapper: (inputs_embeds [B, P + L, E] = prefix ‖
+        wte[input_ids], key mask [B, P + L] with ones for the prefix, shifted targets [B, P + L] or None).
+        Plain torch ops on the prefix, so autograd follows it (vcap/train.py)."""
         dev = self.hip.device
         B, P = prefix.shape[0], prefix.shape[1]
         ids = input_ids.to(dev).long()
@@ -172,7 +171,16 @@ class HipTextDecoder:
             # HF shifts inside the model: the logits at position i are scored against label i + 1
             ext = torch.cat([torch.full((B, P), -100, dtype=torch.long, device=dev), labels.to(dev).long()], dim=1)
             targets = torch.cat([ext[:, 1:], torch.full((B, 1), -100, dtype=torch.long, device=dev)], dim=1)
-        return self.hip.score(x, km, targets, want_logits=want_logits, check_mask=P == 0)
+        return x, km, targets
+
+    @torch.no_grad()
+    def forward_from_prefix(self, prefix: torch.Tensor, input_ids: torch.Tensor,
+                            attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                            want_logits: bool = True):
+        """GPT2TextDecoder.forward after the mapper: prefix [B, P, E] -> vcap.model.ScoreResult over the
+        P + L positions (one vcap_gpt2_score pass per chunk of sequences)."""
+        x, km, targets = self.score_inputs(prefix, input_ids, attention_mask, labels)
+        return self.hip.score(x, km, targets, want_logits=want_logits, check_mask=prefix.shape[1] == 0)
 
     @torch.no_grad()
     def forward(self, video_emb: torch.Tensor, input_ids: torch.Tensor,

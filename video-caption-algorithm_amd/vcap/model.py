@@ -532,6 +532,105 @@ class HipGPT2Decoder:
                 nll_sum, count = nll_sum + pairs[ci, 0], count + pairs[ci, 1]
         return ScoreResult(logits, logprobs, nll_sum, count)
 
+    def enable_grad(self, sd: Dict[str, np.ndarray]) -> int:
+        """Upload the weight copies vcap_gpt2_score_backward reads and build its grad desc (once; later
+        calls return at once).  `sd` is the state dict the decoder was built from.  Inference memory is
+        unchanged until this is called.  Returns the bytes added: per layer the four Conv1D [in, out]
+        matrices as stored (12 E^2 elements) and the Linear-layout copies of c_attn and c_fc (7 E^2), plus wte
+        transposed and padded ([E, ceil(V / 128) * 128]) - GPT-2-small: 0.35 GB in bf16 (0.25 GB of it the
+        Conv1D copies and wte^T), 0.70 GB in fp32."""
+        if getattr(self, "grad_desc", None) is not None:
+            return self.grad_bytes
+        dev, tdt = self.device, _dtype(self.precision)[1]
+        p = "decoder.model.transformer."
+        keep: List[torch.Tensor] = []
+
+        def up(a: torch.Tensor) -> int:
+            t = a.to(dev).to(tdt).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        def mat(k):
+            return torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32))
+
+        V, E = self.arch.vocab, self.arch.n_embd
+        vpad = (V + 127) // 128 * 128
+        wte_t = torch.zeros(E, vpad, dtype=torch.float32)
+        wte_t[:, :V] = mat(p + "wte.weight").t()
+        layers = (N.GPT2GradLayer * self.arch.n_layer)()
+        for i in range(self.arch.n_layer):
+            b = f"{p}h.{i}."
+            ly = layers[i]
+            attn, fc = mat(b + "attn.c_attn.weight"), mat(b + "mlp.c_fc.weight")
+            ly.attn_c, ly.aproj_c = up(attn), up(mat(b + "attn.c_proj.weight"))
+            ly.fc_c, ly.mproj_c = up(fc), up(mat(b + "mlp.c_proj.weight"))
+            ly.attn_l, ly.fc_l = up(attn.t()), up(fc.t())
+        self._grad_layers = layers
+        self.grad_desc = N.GPT2GradDesc(dtype=self.dt, n_embd=E, n_layer=self.arch.n_layer, vocab_pad=vpad,
+                                        wte_t=up(wte_t), layers=layers)
+        self._grad_keep = keep
+        self.grad_bytes = sum(t.numel() * t.element_size() for t in keep)
+        torch.cuda.synchronize(dev)
+        return self.grad_bytes
+
+    @torch.no_grad()
+    def score_backward(self, embeds: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
+                       targets: Optional[torch.Tensor] = None, grad_logprob: Optional[torch.Tensor] = None,
+                       check_mask: bool = True) -> Tuple["ScoreResult", torch.Tensor]:
+        """score() with targets, plus grad_embeds [B, S, E] = sum over the counted positions of
+        grad_logprob[b, i] * d logprobs[b, i] / d embeds (grad_logprob None: -1 everywhere, the gradient of
+        nll_sum) - one vcap_gpt2_score_backward call per chunk of sequences, chunked exactly as score()
+        chunks.  A sequence's gradient bits do not depend on the other sequences of its call, so the chunked
+        result equals the one-call bits.  Needs enable_grad(sd) first.  Returns (ScoreResult without
+        logits, grad_embeds); logprobs and the loss pair are score()'s bits."""
+        if getattr(self, "grad_desc", None) is None:
+            raise N.VcapError("score_backward: call enable_grad(sd) first", N.E_ARG)
+        if targets is None:
+            raise ValueError("score_backward: targets are required")
+        x = embeds.to(self.device, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] != self.arch.n_embd:
+            raise ValueError(f"embeds shape {tuple(x.shape)} != [B, S, {self.arch.n_embd}]")
+        B, S, _ = x.shape
+        max_rows = int(N.lib().vcap_gpt2_max_rows())
+        if B < 1 or S < 1 or S > max_rows or S > self.arch.n_positions:
+            raise N.VcapError(f"score_backward: S = {S} exceeds vcap_gpt2_max_rows() = {max_rows} or n_positions",
+                              N.E_UNSUPPORTED)
+        km = gw = None
+        if key_mask is not None:
+            km = (key_mask != 0).to(self.device, torch.uint8).contiguous()
+            if tuple(km.shape) != (B, S):
+                raise ValueError(f"key_mask shape {tuple(km.shape)} != {(B, S)}")
+            if check_mask and not bool(km[:, 0].all()):
+                raise N.VcapError("score_backward: key_mask[:, 0] must be nonzero (a row with no visible key)",
+                                  N.E_ARG)
+        tg = targets.to(self.device, torch.int32).contiguous()
+        if tuple(tg.shape) != (B, S):
+            raise ValueError(f"targets shape {tuple(tg.shape)} != {(B, S)}")
+        if grad_logprob is not None:
+            gw = grad_logprob.to(self.device, torch.float32).contiguous()
+            if tuple(gw.shape) != (B, S):
+                raise ValueError(f"grad_logprob shape {tuple(gw.shape)} != {(B, S)}")
+        logprobs = torch.empty(B, S, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(x)
+        per = max(1, max_rows // S)
+        starts = list(range(0, B, per))
+        pairs = torch.empty(len(starts), 2, dtype=torch.float32, device=self.device)
+        stream = _stream(self.device)
+        lib = N.lib()
+        for ci, b0 in enumerate(starts):
+            nb = min(per, B - b0)
+            ws = self.ws.get(int(lib.vcap_gpt2_score_backward_workspace_bytes(C.byref(self.desc),
+                                                                              C.byref(self.grad_desc), nb, S)))
+            N.check(lib.vcap_gpt2_score_backward(C.byref(self.desc), C.byref(self.grad_desc), x[b0:].data_ptr(), nb, S,
+                                                 N.ptr(None if km is None else km[b0:]), tg[b0:].data_ptr(),
+                                                 N.ptr(None if gw is None else gw[b0:]), grad[b0:].data_ptr(),
+                                                 logprobs[b0:].data_ptr(), pairs[ci].data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), stream), "vcap_gpt2_score_backward")
+        nll_sum, count = pairs[0, 0], pairs[0, 1]
+        for ci in range(1, len(starts)):   # chunk order, as score()
+            nll_sum, count = nll_sum + pairs[ci, 0], count + pairs[ci, 1]
+        return ScoreResult(None, logprobs, nll_sum, count), grad
+
     def _beam_ids(self, prefix, prompt_ids, cfg: GenConfig, out, workspace, lengths_out):
         B, P, E = prefix.shape
         if P != self.prefix_len or E != self.arch.n_embd:
