@@ -647,6 +647,63 @@ int vcap_text_encode(const vcap_text_desc* d, const int* ids /* device [B][L] */
                      float* hidden_out /* optional device [B][L][dim]: the encoder output before the pool */,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- text tower training (added within ABI v16: new symbols and structs only): the gradient of any scalar of
+ *      vcap_text_encode's unit-norm `out` rows with respect to every text-tower parameter - autograd of
+ *      ViTTextAlignModel.encode_text in eval mode (no dropout).  One call runs vcap_text_encode's schedule,
+ *      keeping per layer the f32 stream at the layer input, the two pre-LayerNorm sums, the LN1 output, q | k | v,
+ *      the attention output and the ReLU output, then walks the layers last to first.  `out` has
+ *      vcap_text_encode's bits.
+ *        grad_out    device [B][proj_dim] f32: d scalar / d out
+ *        grads       device f32 tensors in torch's own layouts ([out, in]); every pointer required
+ *        emb_ids / emb_rows / emb_count   the row-sparse embedding gradient: emb_ids[0 .. count) = the distinct
+ *                    ids of the call that are neither pad_id nor outside the vocabulary, ascending; emb_rows[i] =
+ *                    the f32 sum of the layer-0 input gradient over the positions holding emb_ids[i], in
+ *                    ascending flat position b * L + l, from +0; entries count .. B*L-1 are id -1 with zero rows
+ *      The grad desc holds operand-dtype, plain row-major TRANSPOSED ([in, out]) copies of the four
+ *      projection weights of each layer: every dx = dy . W is then C = A . Wt^T on the 128x128 MFMA tile
+ *      kernel.  Weight gradients dW = dY^T . X run on the same kernel over operand-dtype transposed copies
+ *      dY^T [N][Mpad], X^T [K][Mpad] (Mpad = B*L rounded up to the K tile, 32 rows f32 / 64 bf16, the pad
+ *      columns +0).  No float atomics; every sum over the B*L rows has one order that depends on the model
+ *      shape and (B, L) only: K tiles in order inside constant slabs of 128 rows added in slab order (weights);
+ *      rows w, w + 4, ... per wave w = 0..3, the four partial sums added in wave order (biases, gamma / beta);
+ *      captions in order (proj_w, proj_b).  A caption with no non-pad position contributes exactly +0 to
+ *      everything upstream of the pool.  An id outside [0, vocab) is never used as an index; it makes the
+ *      call's weight gradients NaN.  bf16: every MFMA operand is bf16 (RNE); accumulation, the residual gradient,
+ *      the attention, LayerNorm and tail arithmetic are f32; an f32 desc rounds nowhere.
+ *      Limits and return codes are vcap_text_encode's, refused before the first launch; a grad desc whose
+ *      dtype / dim / ffn / n_layer differ from the text desc's and null gradient or weight pointers are
+ *      VCAP_E_ARG, a short workspace VCAP_E_WORKSPACE; the workspace query returns 0 outside the limits.
+ *      n_layer == 0 works (embedding -> pool -> proj).  6 + 46 * n_layer launches and device copies (50 * n_layer
+ *      with bf16 operands: the row gradients' bf16 copies). ---- */
+typedef struct vcap_text_grad_layer {     /* operand dtype, row-major [in, out] */
+  const void* in_t;    /* [E, 3E] = in_proj_weight^T  */
+  const void* out_t;   /* [E, E]  = out_proj.weight^T */
+  const void* fc1_t;   /* [E, F]  = linear1.weight^T  */
+  const void* fc2_t;   /* [F, E]  = linear2.weight^T  */
+} vcap_text_grad_layer;
+typedef struct vcap_text_grad_desc {
+  int dtype, dim, ffn, n_layer;           /* must equal the text desc's */
+  const vcap_text_grad_layer* layers;     /* host array of n_layer entries; may be NULL when n_layer == 0 */
+} vcap_text_grad_desc;
+typedef struct vcap_text_param_grads_layer {   /* device f32 */
+  float* in_w;  float* in_b;    /* [3E, E], [3E] */
+  float* out_w; float* out_b;   /* [E, E], [E]   */
+  float* ln1_g; float* ln1_b;
+  float* fc1_w; float* fc1_b;   /* [F, E], [F]   */
+  float* fc2_w; float* fc2_b;   /* [E, F], [E]   */
+  float* ln2_g; float* ln2_b;
+} vcap_text_param_grads_layer;
+typedef struct vcap_text_param_grads {
+  float* proj_w; float* proj_b;           /* [proj_dim, dim], [proj_dim] */
+  int* emb_ids; float* emb_rows;          /* [B*L], [B*L][dim] */
+  int* emb_count;                         /* device scalar */
+  const vcap_text_param_grads_layer* layers;   /* host array of n_layer entries */
+} vcap_text_param_grads;
+size_t vcap_text_encode_backward_workspace_bytes(const vcap_text_desc* d, const vcap_text_grad_desc* g, int B, int L);
+int vcap_text_encode_backward(const vcap_text_desc* d, const vcap_text_grad_desc* g, const int* ids /* device */,
+                              int B, int L, const float* grad_out, const vcap_text_param_grads* grads,
+                              float* out /* device [B][proj_dim] */, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- ragged prompts (added within ABI v16: new symbols and one struct only): one device decode for B
  *      rows with a prompt each.  The contract is per row: row b's tokens, raw logits, warped scores and
  *      beam result are those of the uniform entry point (vcap_gpt2_generate / _sample / _beam_search)

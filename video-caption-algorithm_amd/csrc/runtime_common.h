@@ -78,6 +78,18 @@ int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int 
                        const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
                        float* snap, hipStream_t s, ScoreForward* out);
 
+// ---- runtime_text.hip, for the text tower's backward (runtime_text_grad.hip)
+int vcap_text_limits(const vcap_text_desc* d, int B, int L, const char* who);
+int vcap_text_check_pointers(const vcap_text_desc* d, const void* workspace);
+struct TextSnap {   // what the forward keeps for the backward, layer-major (M = B * L rows, T = the operand dtype)
+  float* x;         // [n_layer][4][M][E] f32 stream: layer input, pre-LN1 sum, LN1 output, pre-LN2 sum
+  char* qkv;        // [n_layer][M][3E] T
+  char* attn;       // [n_layer][M][E] T
+  char* act;        // [n_layer][M][F] T
+};
+int vcap_text_forward(const vcap_text_desc* d, const int* ids, int B, int L, float* out, float* hidden_out,
+                      void* workspace, const TextSnap* snap, hipStream_t s);
+
 // ---- graph_cache.hip
 // Bytes of everything a captured decode bakes in; two calls replay one graph only if their keys are equal.
 struct GraphKey {

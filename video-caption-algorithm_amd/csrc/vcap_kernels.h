@@ -212,6 +212,7 @@ hipError_t vcap_score_combine_dispatch(const ScoreLmArgs& a, const uint8_t* kmas
 // the K step.  k_per_slab > 0: K range z of that many columns goes to the slab C + z * M * ldc
 // (ceil(K / k_per_slab) slabs).  vcap_grad_slab_sum_dispatch: out [n] = the slabs added in slab order, then
 // + bias [N] (rows of N columns) and, round_bf16, rounded to bf16 values.
+int vcap_grad_bk(int dt);   // the tile kernel's K step in elements: 32 f32, 64 bf16
 hipError_t vcap_grad_gemm_dispatch(int dt, const void* A, long lda, const void* W, long ldw, float* C, long ldc,
                                    int M, int N, int K, int k_per_slab, hipStream_t s);
 hipError_t vcap_grad_slab_sum_dispatch(const float* slabs, long n, int nslab, const float* bias, int N,
@@ -350,6 +351,31 @@ hipError_t vcap_text_resid_ln_dispatch(int dt, float* x, void* xt, const float* 
 // out [B, P] = normalize(pw . mean over ids != pad of x + pb), eps 1e-12; P % 64 == 0, 64 <= P <= 1024
 hipError_t vcap_text_pool_dispatch(const float* x, const int* ids, int pad_id, int B, int L, int E, const float* pw,
                                    const float* pb, int P, float* out, hipStream_t s);
+
+// ---- text tower backward (csrc/text_backward.hip): parameter gradients, f32 outputs, fixed orders ----
+// dy [B, P], pooled [B, E] and g [M, E] (the gradient at the encoder output) from gout [B, P] at the forward's
+// out; then dproj_w [P, E] and dproj_b [P], captions in order
+hipError_t vcap_text_tail_bwd_dispatch(const float* x, const int* ids, int pad_id, int B, int L, int E,
+                                       const float* pw, const float* pb, int P, const float* out, const float* gout,
+                                       float* dy, float* pooled, float* g, float* dproj_w, float* dproj_b,
+                                       hipStream_t s);
+// dx [M, E] = the LayerNorm input gradient of dy = a (+ b; b may be null) at the rows x; a <- dy; stats [M, 2];
+// dgamma, dbeta [E] summed over the rows in a fixed order
+hipError_t vcap_text_ln_bwd_dispatch(const float* x, float* a, const float* b, const float* gamma, float eps, int M,
+                                     int E, float* dx, float* stats, float* dgamma, float* dbeta, hipStream_t s);
+// out [N] = sum over the M rows of src [M, N] in a fixed order; N % 64 == 0
+hipError_t vcap_text_colsum_dispatch(const float* src, int M, int N, float* out, hipStream_t s);
+// dst (dt) [N, Mpad] = src^T, src [M, N] f32 (src_f32) or dt; columns m >= M are +0; N % 64 == 0, Mpad % 32 == 0
+hipError_t vcap_text_transpose_dispatch(int dt, int src_f32, const void* src, int M, int N, int Mpad, void* dst,
+                                        hipStream_t s);
+// d [n] <- d where act (dt) > 0, else +0
+hipError_t vcap_text_relu_bwd_dispatch(int dt, const void* act, long n, float* d, hipStream_t s);
+// qkv (dt) [B*L, 3 * 64 H], dO f32 [B*L, 64 H]; P, dS: [B*H, L, L] f32 scratch; dqkv f32 [B*L, 3 * 64 H]; no mask
+hipError_t vcap_text_attn_bwd_dispatch(int dt, const void* qkv, const float* dO, int B, int L, int H, float* P,
+                                       float* dS, float* dqkv, hipStream_t s);
+// the row-sparse embedding gradient of dx0 = a (+ b): slot [M] scratch, emb_ids [M], count [1], rows [M, E]; M <= 512
+hipError_t vcap_text_emb_grad_dispatch(const int* ids, int M, int pad_id, int vocab, const float* a, const float* b,
+                                       int E, int* slot, int* emb_ids, int* count, float* rows, hipStream_t s);
 
 // JPEG frame decode (jpeg.hip): header of one baseline image, workspace of n same-shape images,
 // host entropy decode + device IDCT / upsampling / colour conversion into uint8 [n, H, W, 3].

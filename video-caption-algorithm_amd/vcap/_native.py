@@ -102,6 +102,24 @@ class TextDesc(C.Structure):
                 ("layers", C.POINTER(TextLayer))]
 
 
+class TextGradLayer(C.Structure):
+    _fields_ = [("in_t", vp), ("out_t", vp), ("fc1_t", vp), ("fc2_t", vp)]
+
+
+class TextGradDesc(C.Structure):
+    _fields_ = [("dtype", i32), ("dim", i32), ("ffn", i32), ("n_layer", i32), ("layers", C.POINTER(TextGradLayer))]
+
+
+class TextParamGradsLayer(C.Structure):
+    _fields_ = [("in_w", vp), ("in_b", vp), ("out_w", vp), ("out_b", vp), ("ln1_g", vp), ("ln1_b", vp),
+                ("fc1_w", vp), ("fc1_b", vp), ("fc2_w", vp), ("fc2_b", vp), ("ln2_g", vp), ("ln2_b", vp)]
+
+
+class TextParamGrads(C.Structure):
+    _fields_ = [("proj_w", vp), ("proj_b", vp), ("emb_ids", vp), ("emb_rows", vp), ("emb_count", vp),
+                ("layers", C.POINTER(TextParamGradsLayer))]
+
+
 # name -> (restype, argtypes); every symbol include/vcap.h declares
 SIGNATURES = {
     "vcap_last_error": (C.c_char_p, []),
@@ -173,6 +191,9 @@ SIGNATURES = {
     "vcap_ivf_search": (i32, [i32, vp, vp, vp, i64, vp, i32, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, i32, vp]),
     "vcap_text_workspace_bytes": (sz, [C.POINTER(TextDesc), i32, i32]),
     "vcap_text_encode": (i32, [C.POINTER(TextDesc), vp, i32, i32, vp, vp, vp, sz, vp]),
+    "vcap_text_encode_backward_workspace_bytes": (sz, [C.POINTER(TextDesc), C.POINTER(TextGradDesc), i32, i32]),
+    "vcap_text_encode_backward": (i32, [C.POINTER(TextDesc), C.POINTER(TextGradDesc), vp, i32, i32, vp,
+                                        C.POINTER(TextParamGrads), vp, vp, sz, vp]),
     "vcap_gpt2_ragged_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(C.c_int), i32, i32]),
     "vcap_gpt2_generate_ragged": (i32, [C.POINTER(GPT2Desc), C.POINTER(GenParams), vp, C.POINTER(Prompts), i32, vp,
                                         vp, vp, sz, vp]),

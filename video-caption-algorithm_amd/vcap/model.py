@@ -113,6 +113,7 @@ class HipViTEncoder:
         }
         for v in t.values():
             keep(v)
+        self.proj_w, self.proj_b = t["proj_w"], t["proj_b"]   # encoder.proj, rewritable in place (train_align)
         self.layers = (N.VitLayer * arch.depth)()
         for i in range(arch.depth):
             b = f"{p}blocks.{i}."

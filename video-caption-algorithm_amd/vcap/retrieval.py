@@ -650,11 +650,18 @@ class HipTextEmbedder:
         self.pad_id, self.nhead, self.dtype, self.device = int(pad_id), int(nhead), dtype, torch.device(device)
         self.dt, tdt = _TEXT_DTYPE[dtype]
         self._keep: List[torch.Tensor] = []
+        self._f32: Dict[str, torch.Tensor] = {}      # name -> the f32 device tensor the descriptor points at
+        self._packed: Dict[str, torch.Tensor] = {}   # name -> the rows-packed operand copy
+        self._tr: Dict[str, torch.Tensor] = {}       # name -> the transposed operand copy (enable_grad)
+        self._host_w: Dict[str, np.ndarray] = {}     # projection weights until enable_grad uploads their transposes
+        self.grad_desc = None
+        self._gws: Optional[torch.Tensor] = None
         dev = self.device
 
         def f32(k):
             t = torch.from_numpy(sd[k]).to(dev).contiguous()
             self._keep.append(t)
+            self._f32[k] = t
             return t
 
         def packed(k):  # [N, K] Linear weight -> operand dtype -> rows-packed (vcap_rows_pack)
@@ -667,6 +674,8 @@ class HipTextEmbedder:
             N.check(N.lib().vcap_rows_pack(self.dt, w.data_ptr(), w.stride(0), rows, kk, p.data_ptr(), _stream(dev)),
                     "vcap_rows_pack")
             self._keep.append(p)
+            self._packed[k] = p
+            self._host_w[k] = sd[k]
             return p
 
         self.layers = (N.TextLayer * max(self.n_layer, 1))()
@@ -727,6 +736,155 @@ class HipTextEmbedder:
                                          N.ptr(hidden[s:s + n]) if return_hidden else None, self._ws.data_ptr(),
                                          self._ws.numel(), _stream(self.device)), "vcap_text_encode")
         return (out, hidden) if return_hidden else out
+
+    # ---- training: vcap_text_encode_backward
+    _PROJ = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight")
+    _LAYER_GRADS = (("in_w", "self_attn.in_proj_weight"), ("in_b", "self_attn.in_proj_bias"),
+                    ("out_w", "self_attn.out_proj.weight"), ("out_b", "self_attn.out_proj.bias"),
+                    ("ln1_g", "norm1.weight"), ("ln1_b", "norm1.bias"), ("fc1_w", "linear1.weight"),
+                    ("fc1_b", "linear1.bias"), ("fc2_w", "linear2.weight"), ("fc2_b", "linear2.bias"),
+                    ("ln2_g", "norm2.weight"), ("ln2_b", "norm2.bias"))
+
+    def param_names(self) -> List[str]:
+        """The state dict's names of the tower's parameters, in the state dict's order."""
+        names = ["txt_emb.weight"]
+        for i in range(self.n_layer):
+            names += [f"txt_enc.layers.{i}.{k}" for _, k in self._LAYER_GRADS]
+        return names + ["txt_proj.weight", "txt_proj.bias"]
+
+    def enable_grad(self) -> "HipTextEmbedder":
+        """Upload the operand-dtype transposed ([in, out]) copies of the projection weights the backward's
+        dx = dy . W products read (from the host copies kept since construction / the last load_state_dict)."""
+        if self.grad_desc is not None:
+            return self
+        tdt = _TEXT_DTYPE[self.dtype][1]
+        self._glayers = (N.TextGradLayer * max(self.n_layer, 1))()
+        for i in range(self.n_layer):
+            b = f"txt_enc.layers.{i}."
+            for field, k in zip(("in_t", "out_t", "fc1_t", "fc2_t"), self._PROJ):
+                rows, kk = self._shape_of(b + k)
+                t = torch.from_numpy(self._host_w[b + k]).to(self.device).to(tdt).t().contiguous()
+                self._tr[b + k] = t
+                setattr(self._glayers[i], field, t.data_ptr())
+        self.grad_desc = N.TextGradDesc(dtype=self.dt, dim=self.dim, ffn=self.ffn, n_layer=self.n_layer,
+                                        layers=self._glayers)
+        self._host_w = {}          # the transposed copies follow load_state_dict from here on
+        return self
+
+    def _shape_of(self, k: str):
+        E, F = self.dim, self.ffn
+        return {"self_attn.in_proj_weight": (3 * E, E), "self_attn.out_proj.weight": (E, E),
+                "linear1.weight": (F, E), "linear2.weight": (E, F)}[k.split(".", 3)[3]]
+
+    def load_state_dict(self, sd) -> None:
+        """Rewrite every device weight in place from `sd` (numpy or torch values under the state dict's
+        names): the f32 tensors, the rows-packed forward operands and, after enable_grad, the transposed
+        copies.  No pointer of desc / grad_desc changes and nothing is reallocated."""
+        tdt = _TEXT_DTYPE[self.dtype][1]
+        if isinstance(sd, dict) and "model_state" in sd:
+            sd = sd["model_state"]
+        lib = N.lib()
+
+        def dev(k):
+            v = sd[k]
+            v = v.detach() if hasattr(v, "detach") else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            return v.to(device=self.device, dtype=torch.float32)
+
+        for k, t in self._f32.items():
+            v = dev(k)
+            if v.shape != t.shape:
+                raise ValueError(f"{k}: shape {tuple(v.shape)} does not match the embedder's {tuple(t.shape)}")
+            t.copy_(v)
+        for k, p in self._packed.items():
+            w = dev(k).to(tdt).contiguous()
+            rows, kk = w.shape
+            if (rows, kk) != self._shape_of(k):
+                raise ValueError(f"{k}: shape {tuple(w.shape)} does not match the embedder's")
+            N.check(lib.vcap_rows_pack(self.dt, w.data_ptr(), w.stride(0), rows, kk, p.data_ptr(), _stream(self.device)),
+                    "vcap_rows_pack")
+            if k in self._tr:
+                self._tr[k].copy_(w.t())
+            else:
+                self._host_w[k] = dev(k).cpu().numpy()
+
+    def _backward_chunk(self, t: torch.Tensor, g: torch.Tensor, out: torch.Tensor) -> Dict[str, object]:
+        """One vcap_text_encode_backward call: ids t [n, L] int32, grad_out g [n, P] -> out [n, P] filled;
+        returns {name: f32 tensor}, the embedding gradient as (ids int64 [count], rows [count, E]), and the
+        ABI's untrimmed (emb_ids [M], emb_rows [M, E], count)."""
+        n, L = t.shape
+        M, E, F, P, lib, dev = n * L, self.dim, self.ffn, self.proj_dim, N.lib(), self.device
+        shapes = {"in_w": (3 * E, E), "in_b": (3 * E,), "out_w": (E, E), "out_b": (E,), "ln1_g": (E,), "ln1_b": (E,),
+                  "fc1_w": (F, E), "fc1_b": (F,), "fc2_w": (E, F), "fc2_b": (E,), "ln2_g": (E,), "ln2_b": (E,)}
+        res: Dict[str, object] = {}
+        glayers = (N.TextParamGradsLayer * max(self.n_layer, 1))()
+        for i in range(self.n_layer):
+            for field, k in self._LAYER_GRADS:
+                buf = torch.empty(shapes[field], dtype=torch.float32, device=dev)
+                res[f"txt_enc.layers.{i}.{k}"] = buf
+                setattr(glayers[i], field, buf.data_ptr())
+        pw = torch.empty(P, E, dtype=torch.float32, device=dev)
+        pb = torch.empty(P, dtype=torch.float32, device=dev)
+        eids = torch.empty(M, dtype=torch.int32, device=dev)
+        erows = torch.empty(M, E, dtype=torch.float32, device=dev)
+        cnt = torch.empty(1, dtype=torch.int32, device=dev)
+        grads = N.TextParamGrads(proj_w=pw.data_ptr(), proj_b=pb.data_ptr(), emb_ids=eids.data_ptr(),
+                                 emb_rows=erows.data_ptr(), emb_count=cnt.data_ptr(), layers=glayers)
+        need = int(lib.vcap_text_encode_backward_workspace_bytes(C.byref(self.desc), C.byref(self.grad_desc), n, L))
+        if need == 0:
+            raise N.VcapError(f"vcap_text_encode_backward_workspace_bytes refused B={n}, L={L}: "
+                              f"{(lib.vcap_last_error() or b'').decode()}")
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = torch.empty(need, dtype=torch.uint8, device=dev)
+        N.check(lib.vcap_text_encode_backward(C.byref(self.desc), C.byref(self.grad_desc), t.data_ptr(), n, L,
+                                              g.data_ptr(), C.byref(grads), out.data_ptr(), self._gws.data_ptr(),
+                                              self._gws.numel(), _stream(dev)), "vcap_text_encode_backward")
+        c = int(cnt.item())
+        res["txt_emb.weight"] = (eids[:c].long(), erows[:c])
+        res["txt_proj.weight"], res["txt_proj.bias"] = pw, pb
+        return res, (eids, erows, c)
+
+    def encode_text_backward(self, ids, grad_out):
+        """ids [B, L], grad_out [B, proj_dim] (d scalar / d out) -> (out [B, proj_dim], grads).  grads maps the
+        state dict's names to f32 device tensors in torch's layouts; "txt_emb.weight" comes back row-sparse as
+        (ids int64 [count] ascending, rows [count, dim]) - embedding_grad_dense() scatters it.  Batches of more
+        than max_rows / L captions go in chunks whose gradients are added in chunk order, the embedding rows
+        merged by id."""
+        if self.grad_desc is None:
+            raise RuntimeError("encode_text_backward needs enable_grad() first")
+        t = self._ids(ids)
+        B, L = t.shape
+        g = torch.as_tensor(grad_out).to(device=self.device, dtype=torch.float32).contiguous()
+        if g.shape != (B, self.proj_dim):
+            raise ValueError(f"grad_out must be [{B}, {self.proj_dim}], got {tuple(g.shape)}")
+        out = torch.empty(B, self.proj_dim, dtype=torch.float32, device=self.device)
+        per, total = max(1, self.max_rows // L), None
+        for s in range(0, B, per):
+            n = min(per, B - s)
+            part, _ = self._backward_chunk(t[s:s + n], g[s:s + n], out[s:s + n])
+            total = part if total is None else self._merge(total, part)
+        return out, total
+
+    @staticmethod
+    def _merge(a: Dict[str, object], b: Dict[str, object]) -> Dict[str, object]:
+        res: Dict[str, object] = {}
+        for k, v in a.items():
+            if k != "txt_emb.weight":
+                res[k] = v + b[k]
+                continue
+            (ia, ra), (ib, rb) = v, b[k]
+            ids = torch.unique(torch.cat([ia, ib]))          # sorted
+            rows = torch.zeros(ids.numel(), ra.shape[1], dtype=ra.dtype, device=ra.device)
+            rows.index_copy_(0, torch.searchsorted(ids, ia), ra)        # each chunk's ids are distinct
+            rows.index_add_(0, torch.searchsorted(ids, ib), rb)         # distinct too: one add per row
+            res[k] = (ids, rows)
+        return res
+
+    def embedding_grad_dense(self, sparse) -> torch.Tensor:
+        """(ids, rows) -> the dense [vocab, dim] gradient of txt_emb.weight: zeros but the listed rows (the
+        ids are distinct, so index_copy_ is deterministic; the pad row stays zero)."""
+        ids, rows = sparse
+        dense = torch.zeros(self.vocab, self.dim, dtype=torch.float32, device=rows.device)
+        return dense.index_copy_(0, ids, rows)
 
 
 class HipAlignModel:
