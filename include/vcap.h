@@ -417,8 +417,8 @@ int vcap_gpt2_score(const vcap_gpt2_desc* d, const float* embeds, int B, int S, 
 /* ---- the scoring call's gradient w.r.t. inputs_embeds (added within ABI v16: new symbols and two new structs,
  *      nothing existing changes): vcap_gpt2_score's forward, then an activation-only backward through the
  *      frozen GPT-2 - what fitting a prefix mapper, soft prompts or an embedding saliency needs (the
- *      reference's recipe: src/cli/train_caption_mapper.py compute_loss_local, GPT-2 and ViT frozen).  No
- *      weight gradients exist on the device.
+ *      reference's recipe: src/cli/train_caption_mapper.py compute_loss_local, GPT-2 and ViT frozen).  This
+ *      call returns no weight gradients; vcap_gpt2_score_backward_tail below adds those of the last blocks.
  *        embeds, key_mask, targets, logprob_out, loss_out: exactly vcap_gpt2_score's, the precondition
  *                    key_mask[b][0] != 0 included; targets is required here
  *        grad_logprob [B, S] f32 or NULL: the weight w[b][i] of each counted position's log-prob lp[b][i];
@@ -476,6 +476,64 @@ int vcap_gpt2_score_backward(const vcap_gpt2_desc* d, const vcap_gpt2_grad_desc*
                              const uint8_t* key_mask, const int* targets, const float* grad_logprob,
                              float* grad_embeds, float* logprob_out, float* loss_out, void* workspace,
                              size_t ws_bytes, void* stream);
+
+/* ---- GPT-2 tail fine-tuning (added within ABI v16: new symbols and two new structs, nothing existing
+ *      changes): vcap_gpt2_score_backward plus the gradient of the same objective with respect to every
+ *      parameter of the last n_tail blocks - the reference's --unfreeze_gpt2_last N
+ *      (src/cli/train_caption_mapper.py: block.parameters() of transformer.h[-N:]; ln_f, wte and wpe stay
+ *      frozen).  One walk serves both entry points: this call is that walk with side outputs, so
+ *        - grad_embeds (required here too: the mapper trains as well), logprob_out and loss_out are
+ *          bit-identical to vcap_gpt2_score_backward's on the same inputs.
+ *      param_grads->layers[i] holds the 12 device f32 outputs of layer n_layer - n_tail + i in HF's own
+ *      layouts (Conv1D weights [in, out]); they are written, not accumulated.  In an unfrozen layer the walk
+ *      emits, from operands it holds at that point (T = the decoder dtype):
+ *          d mproj_w = act^T . g    d mproj_b = colsum(g)       act = gelu_new(c_fc), the forward's own bits
+ *          d fc_w    = xn2^T . du   d fc_b    = colsum(du)      xn2 = ln_2(x1) recomputed, du = dact gelu'(u)
+ *          d ln2_g   = sum_m dy xhat(x1)   d ln2_b = sum_m dy   dy = du . c_fc^T (f32)
+ *          d aproj_w = att^T . g'   d aproj_b = colsum(g')      att = the forward's attention output, g' = the
+ *                                                              residual gradient after the ln_2 backward
+ *          d attn_w  = xn1^T . dqkv d attn_b  = colsum(dqkv)    xn1 = ln_1(x0) recomputed
+ *          d ln1_g, d ln1_b likewise from dy = dqkv . c_attn^T and x0
+ *      g / g' enter as the T copy the c_proj^T products already read (bf16: RNE of the f32 stream).  act and
+ *      att are two more copies per unfrozen layer taken between the forward's launches (M * 5E elements of T
+ *      per layer); frozen layers cost nothing, and vcap_gpt2_score / vcap_gpt2_score_backward take none.
+ *      Each product dW[k][n] = sum_m X[m][k] dY[m][n] is ONE launch (vcap_gpt2_dw_kernel,
+ *      csrc/gpt2_weight_grad.hip): a workgroup owns a 64 x 128 tile of dW - a function of (K, N) alone - and
+ *      sums all M <= 512 rows in ascending 32-row tiles, X and dY read row-major as they lie and consumed
+ *      column-wise from LDS (bf16: ds_read_b64_tr_b16); rows past M are zero-filled.  No split of the row
+ *      axis, no slabs, no atomics.  Column sums: wave w of a column's workgroup adds rows w, w + 4, ... and the
+ *      four partials are added in wave order.  Accumulation is f32 everywhere; with a bf16 decoder the
+ *      products' operands are bf16 (the call's existing rounding points) and nothing else rounds.
+ *      Contracts beside vcap_gpt2_score_backward's:
+ *        - Deterministic: two calls give the same bits.
+ *        - Linear in grad_logprob: doubling it doubles every parameter gradient bit for bit.
+ *        - Exactly +0 everywhere when no position is counted.
+ *        - Appending sequences with no counted position leaves every parameter gradient bit-identical (their
+ *          dY rows are zeros and no reduction order depends on M).
+ *      Refused before any launch, outputs untouched: vcap_gpt2_score_backward's refusals with its codes;
+ *      n_tail outside 1 .. n_layer, a null struct or any null gradient pointer: VCAP_E_ARG; a small workspace:
+ *      VCAP_E_WORKSPACE (the query returns 0 outside the limits). ---- */
+typedef struct vcap_gpt2_param_grads_layer {   /* device f32, HF's layouts */
+  float *ln1_g, *ln1_b, *attn_w /* [E, 3E] */, *attn_b, *aproj_w /* [E, E] */, *aproj_b;
+  float *ln2_g, *ln2_b, *fc_w /* [E, 4E] */, *fc_b, *mproj_w /* [4E, E] */, *mproj_b;
+} vcap_gpt2_param_grads_layer;
+
+typedef struct vcap_gpt2_param_grads {
+  int n_tail;                                  /* 1 .. n_layer */
+  const vcap_gpt2_param_grads_layer* layers;   /* host array; entry i = layer n_layer - n_tail + i */
+} vcap_gpt2_param_grads;
+
+size_t vcap_gpt2_score_backward_tail_workspace_bytes(const vcap_gpt2_desc* d, const vcap_gpt2_grad_desc* g, int B,
+                                                     int S, int n_tail);
+int vcap_gpt2_score_backward_tail(const vcap_gpt2_desc* d, const vcap_gpt2_grad_desc* g, const float* embeds, int B,
+                                  int S, const uint8_t* key_mask, const int* targets, const float* grad_logprob,
+                                  float* grad_embeds, const vcap_gpt2_param_grads* param_grads, float* logprob_out,
+                                  float* loss_out, void* workspace, size_t ws_bytes, void* stream);
+/* The tail call's product alone (kernel tests and measurements): dW [K, N] f32 = X^T . dY over the M rows of
+ * X [M, K] and dY [M, N], both row-major device memory in `dtype` (VCAP_DT_F32 or VCAP_DT_BF16), 16-byte
+ * aligned.  Rows at and past M are never read.  VCAP_E_ARG: dtype, null / unaligned pointers, sizes < 1;
+ * VCAP_E_UNSUPPORTED: M > vcap_gpt2_max_rows(), K % 64 != 0 or N % 128 != 0. */
+int vcap_gpt2_weight_grad(int dtype, const void* X, const void* dY, float* dW, int M, int K, int N, void* stream);
 
 /* ---- video retrieval (added within ABI v16: new symbols only, no struct changes): the inference half of
  *      the reference's second product - embed a clip, search a flat inner-product index of clip

@@ -1,7 +1,9 @@
 """Fine-tune decoder.mapper on the device path - the reference's src/cli/train_caption_mapper.py with its flag
-names.  ViT and GPT-2 are frozen and run on the HIP kernels; the mapper (0.79 M parameters) is a torch
+names.  The ViT is frozen; it and GPT-2 run on the HIP kernels; the mapper (0.79 M parameters) is a torch
 nn.Linear trained with AdamW on the teacher-forced LM loss, its gradient coming from
-vcap_gpt2_score_backward (vcap/train.py).
+vcap_gpt2_score_backward (vcap/train.py).  --unfreeze_gpt2_last N also trains every parameter of the last N
+GPT-2 blocks, in a second AdamW group at --lr_gpt2, their gradients coming from
+vcap_gpt2_score_backward_tail; the device weights are refreshed in place after every step.
 
 Each clip is embedded ONCE with the frozen device encoder, without gradients; training runs on the cached
 [video_dim] embeddings.  Annotations are the reference's annotations.json records
@@ -11,12 +13,13 @@ tokenise "captions").  Every caption becomes <bos> ids <eos>, truncated to --max
 the pad id (= eos).
 
 Writes <run_dir>/events.csv ("step,loss" per step) and val.csv ("step,val_loss"), and the best checkpoint
-{"model_state": full state dict with the trained decoder.mapper.0.*, "step", "epoch", "best_val", "args"}
+{"model_state": full state dict with the trained decoder.mapper.0.* (and the trained
+decoder.model.transformer.h.{i}.* of an unfrozen tail), "step", "epoch", "best_val", "args"}
 to <ckpt_dir>/<ckpt_name>, which load_caption_model(backend="hip") loads.
 
-Not supported, refused up front: --unfreeze_gpt2_last > 0 and --cond_mode bos (no GPT-2 weight gradient
-exists on the device).  Unlike the reference's .train() on the whole model, the frozen GPT-2 applies no
-dropout noise here; the mapper's own dropout stays.
+Not supported, refused up front: --cond_mode bos (the device decoder conditions on a prefix only).  Unlike
+the reference's .train() on the whole model, the device GPT-2 applies no dropout noise, in the unfrozen
+blocks either; the mapper's own dropout stays.
 
   python -m scripts.train_caption_mapper --ann_train train/annotations.json --ann_val val/annotations.json \\
       --weights_seed 1 --epochs 1
@@ -43,7 +46,8 @@ def build_argparser():
     p.add_argument("--gpt2_name", default="gpt2")
     p.add_argument("--cond_mode", choices=["prefix", "bos"], default="prefix")
     p.add_argument("--prefix_len", type=int, default=4)
-    p.add_argument("--unfreeze_gpt2_last", type=int, default=0)
+    p.add_argument("--unfreeze_gpt2_last", type=int, default=0, help="also train the last N GPT-2 blocks")
+    p.add_argument("--lr_gpt2", type=float, default=1e-5, help="learning rate of the unfrozen GPT-2 blocks")
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--lr", type=float, default=3e-4)
     p.add_argument("--device", default="cuda")
@@ -104,9 +108,8 @@ def batches(rows, emb, batch_size: int, pad_id: int, shuffle: bool, rng: random.
 
 def main(argv=None) -> int:
     args = build_argparser().parse_args(argv)
-    if args.unfreeze_gpt2_last > 0:
-        raise SystemExit("[ERROR] --unfreeze_gpt2_last > 0 is not supported: the device path has no GPT-2 weight "
-                         "gradients (only the mapper trains)")
+    if args.unfreeze_gpt2_last < 0:
+        raise SystemExit("[ERROR] --unfreeze_gpt2_last must be >= 0")
     if args.cond_mode != "prefix":
         raise SystemExit("[ERROR] --cond_mode bos is not supported: the device decoder conditions on a prefix only")
     import torch
@@ -133,10 +136,17 @@ def main(argv=None) -> int:
           f"{len(val_rows)} captions; embedding the clips once")
     train_emb, val_emb = embed_clips(model, train_anns, args), embed_clips(model, val_anns, args)
 
-    trainer = MapperTrainer(model, sd, pad_id=tok.pad_token_id, lr=args.lr, dropout=args.dropout)
+    n_layer = model.decoder.hip.arch.n_layer
+    if args.unfreeze_gpt2_last > n_layer:
+        raise SystemExit(f"[ERROR] --unfreeze_gpt2_last {args.unfreeze_gpt2_last} exceeds the model's {n_layer} blocks")
+    trainer = MapperTrainer(model, sd, pad_id=tok.pad_token_id, lr=args.lr, dropout=args.dropout,
+                            unfreeze_gpt2_last=args.unfreeze_gpt2_last, lr_gpt2=args.lr_gpt2)
     n = sum(p.numel() for p in trainer.mapper.parameters())
     print(f"[trainable] decoder.mapper | params={n:,} | lr={args.lr}; grad copies "
           f"{model.decoder.hip.grad_bytes / 2 ** 20:.0f} MiB")
+    if trainer.tail:
+        n_tail = sum(p.numel() for p in trainer.tail.values())
+        print(f"[trainable] gpt2_tail | params={n_tail:,} | lr={args.lr_gpt2}")
 
     def validate() -> float:
         total, k = 0.0, 0

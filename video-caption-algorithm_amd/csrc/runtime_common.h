@@ -74,9 +74,14 @@ struct ScoreForward {   // what the forward leaves in its workspace for the back
   const float* psum;
   int nparts;
 };
+struct ScoreTailSnap {  // the forward's own att / act bits of the layers >= first_layer, in the decoder dtype
+  void* att;            // [n_layer - first_layer][B*S][E]    the attention output (the attn c_proj's input)
+  void* act;            // [n_layer - first_layer][B*S][4E]   gelu_new(c_fc) (the mlp c_proj's input)
+  int first_layer;
+};
 int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
                        const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
-                       float* snap, hipStream_t s, ScoreForward* out);
+                       float* snap, hipStream_t s, ScoreForward* out, const ScoreTailSnap* tail = nullptr);
 
 // ---- runtime_text.hip, for the text tower's backward (runtime_text_grad.hip)
 int vcap_text_limits(const vcap_text_desc* d, int B, int L, const char* who);

@@ -142,6 +142,10 @@ struct LayerExtras {
   // residual stream [M, E] is copied to snap + 2 l * M * E at layer l's input, to snap + (2 l + 1) * M * E
   // after its attention c_proj and to snap + 2 L * M * E at the last layer's output
   float* snap = nullptr;
+  // the tail call's weight gradients (also host only): in the layers l >= tail->first_layer the attention
+  // output [M, E] and the c_fc output after gelu_new [M, 4E], both in the decoder dtype, are copied to
+  // tail->att / tail->act + (l - first_layer) * their size right after the launch that wrote them
+  const ScoreTailSnap* tail = nullptr;
 };
 
 int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int past, int max_blocks, hipStream_t s,
@@ -176,6 +180,11 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
                           x.row_seq, x.row_pos, x.pos_add, x.seq_len, x.min_len};
     VCAP_TRY(vcap_decode_attention_dispatch(dt, w.q, a.kc, a.vc, keys, w.maxp, w.attn, M, H, S_new, past, s),
              "decode_attention");
+    const bool keep = x.tail && l >= x.tail->first_layer;
+    if (keep)
+      VCAP_TRY(hipMemcpyAsync((char*)x.tail->att + (size_t)(l - x.tail->first_layer) * snap_n * es, w.attn,
+                              snap_n * es, hipMemcpyDeviceToDevice, s),
+               "snapshot");
     // 3) attn c_proj + residual
     RowsGemmArgs b{};
     b.M = M; b.x = w.attn; b.ldx = E; b.w = ly.aproj_w; b.bias = ly.aproj_b; b.N = E; b.K = E;
@@ -188,6 +197,10 @@ int run_layers(const vcap_gpt2_desc* d, const DecState& w, int M, int S_new, int
     c.M = M; c.x = w.h; c.ldx = E; c.ln_g = ly.ln2_g; c.ln_b = ly.ln2_b; c.ln_eps = d->ln_eps;
     c.w = ly.fc_w; c.bias = ly.fc_b; c.N = 4 * E; c.K = E; c.out = w.act; c.ldo = 4 * E; c.max_blocks = max_blocks;
     VCAP_TRY(vcap_rows_gemm_dispatch(dt, PRO_LN, EPI_GELU, c, nullptr, s), "c_fc");
+    if (keep)
+      VCAP_TRY(hipMemcpyAsync((char*)x.tail->act + (size_t)(l - x.tail->first_layer) * 4 * snap_n * es, w.act,
+                              4 * snap_n * es, hipMemcpyDeviceToDevice, s),
+               "snapshot");
     // 5) mlp c_proj + residual, K split at every row count: the arithmetic may not depend on the
     // launch's M (the dispatcher drops the split where it does not apply)
     RowsGemmArgs e{};
@@ -649,10 +662,11 @@ ScoreBufs carve_score(Carver& c, const vcap_gpt2_desc* d, int B, int S) {
 int vcap_gpt2_check_desc(const vcap_gpt2_desc* d, bool launch) { return launch ? check_gpt2_launch(d) : check_gpt2(d); }
 
 // vcap_gpt2_score's schedule (arguments checked by the caller; workspace of vcap_gpt2_score_workspace_bytes).
-// snap / out: the backward's residual-stream snapshots (LayerExtras.snap) and the buffers it reads afterwards.
+// snap / out: the backward's residual-stream snapshots (LayerExtras.snap) and the buffers it reads afterwards;
+// tail: the operand snapshots of the unfrozen layers (LayerExtras.tail), the tail call only.
 int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int S, const uint8_t* key_mask,
                        const int* targets, float* logits_out, float* logprob_out, float* loss_out, void* workspace,
-                       float* snap, hipStream_t s, ScoreForward* out) {
+                       float* snap, hipStream_t s, ScoreForward* out, const ScoreTailSnap* tail) {
   Carver c(workspace);
   const ScoreBufs b = carve_score(c, d, B, S);
   const DecState& w = b.w;
@@ -662,6 +676,7 @@ int vcap_score_forward(const vcap_gpt2_desc* d, const float* embeds, int B, int 
   VCAP_TRY(vcap_prefill_embed_dispatch(d->dtype, embeds, S, nullptr, 0, d->wte, d->wpe, w.h, B, E, s), "embed_inputs");
   LayerExtras x{nullptr, 0, key_mask, S};
   x.snap = snap;
+  x.tail = tail;
   if (int rc = run_layers(d, w, M, S, 0, 0, s, x)) return rc;
   VCAP_TRY(vcap_layernorm_dispatch(d->dtype, w.h, E, b.xn, E, d->lnf_g, d->lnf_b, M, E, d->ln_eps, s), "ln_f");
   ScoreLmArgs a{b.xn, d->wte, M, d->vocab, E, targets, logits_out, b.pmax, b.psum, b.tlogit, b.nparts};

@@ -1,6 +1,8 @@
 // Kernels of vcap_gpt2_score_backward (schedule: runtime_gpt2_grad.hip): the gradient of the
-// teacher-forced target log-probs with respect to inputs_embeds through the frozen GPT-2 - activation
-// gradients only (no weight gradients: every weight, LayerNorm gamma / beta included, is frozen).
+// teacher-forced target log-probs with respect to inputs_embeds through GPT-2 - the activation gradients.
+// (The weight gradients of vcap_gpt2_score_backward_tail's unfrozen blocks are side outputs of the same
+// walk: the products in gpt2_weight_grad.hip, the column sums in text_backward.hip, and the STATS form of
+// vcap_ln_backward_kernel below.)
 //
 //   vcap_grad_gemm_kernel       C[m][n] = sum_k A[m][k] W[n][k] with the 128x128 MFMA tile loop of
 //                               gemm_tile.h, operands in the decoder dtype T, f32 accumulation and f32
@@ -15,7 +17,8 @@
 //   vcap_score_dlogit_kernel    dlogit[m][v] = w[m] (1[v == t_m] - exp(logit[m][v] - lse[m])) in T; rows that
 //                               are not counted and columns past V are written as +0 and cost no exp
 //   vcap_ln_backward_kernel     g[m] += dLN(x[m]) . dy[m]: one row per wave, the row in registers (E <= 1024),
-//                               mean and rstd recomputed from the snapshot x
+//                               mean and rstd recomputed from the snapshot x; <true> also stores them per row
+//                               (an unfrozen layer's gamma / beta column sums read them), same arithmetic for g
 //   vcap_gelu_backward_kernel   du = dact * gelu_new'(u), the derivative of the sigmoid form of gelu_tanh
 //   vcap_attn_bwd_rows_kernel   one wave per (sequence, head, query i): P[i][:], dP = dO_i . V^T, delta_i =
 //                               sum_j P dP, dS = P (dP - delta) / 8 -> the P and dS rows of the call's scratch
@@ -130,11 +133,15 @@ __global__ __launch_bounds__(128) void vcap_score_dlogit_kernel(const float* __r
 }
 
 // g[m][:] += rstd (dyh - mean(dyh) - xh mean(dyh xh)), dyh = dy gamma, xh = (x - mean) rstd.  One row
-// per wave, lane l holds columns 128 k + 2 l + {0, 1}, k < E / 128 <= 8.
+// per wave, lane l holds columns 128 k + 2 l + {0, 1}, k < E / 128 <= 8.  STATS (the tail call's unfrozen
+// layers): the row's (mean, rstd) also go to stats[m] for the gamma / beta column sums; g's arithmetic is
+// the same.
+template <bool STATS>
 __global__ __launch_bounds__(256) void vcap_ln_backward_kernel(const float* __restrict__ x,
                                                                const float* __restrict__ dy,
                                                                const float* __restrict__ gamma, float eps, int M,
-                                                               int E, float* __restrict__ g) {
+                                                               int E, float* __restrict__ g,
+                                                               float* __restrict__ stats) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -163,6 +170,9 @@ __global__ __launch_bounds__(256) void vcap_ln_backward_kernel(const float* __re
       q += fmaf(xv[k].x, xv[k].x, xv[k].y * xv[k].y);
     }
   const float rstd = 1.0f / sqrtf(wave_sum(q) * inv + eps);
+  if constexpr (STATS) {
+    if (lane == 0) *reinterpret_cast<f32x2*>(stats + 2L * row) = (f32x2){mean, rstd};
+  }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k)
@@ -375,7 +385,16 @@ hipError_t vcap_score_dlogit_dispatch(int dt, const float* part_max, const float
 hipError_t vcap_ln_backward_dispatch(const float* x, const float* dy, const float* gamma, float eps, int M, int E,
                                      float* g, hipStream_t s) {
   if (M <= 0 || E <= 0 || E % 128 || E > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vcap_ln_backward_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, dy, gamma, eps, M, E, g);
+  hipLaunchKernelGGL(vcap_ln_backward_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, s, x, dy, gamma, eps, M, E, g,
+                     (float*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t vcap_ln_backward_stats_dispatch(const float* x, const float* dy, const float* gamma, float eps, int M,
+                                           int E, float* g, float* stats, hipStream_t s) {
+  if (M <= 0 || E <= 0 || E % 128 || E > 1024 || !stats) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(vcap_ln_backward_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, x, dy, gamma, eps, M, E, g,
+                     stats);
   return hipGetLastError();
 }
 

@@ -8,7 +8,8 @@
 //   vcap_text_proj_grad_kernel    dproj_w[p][e] = sum over captions in order of dy[b][p] pooled[b][e]; dproj_b
 //   vcap_text_ln_bwd_kernel       the LayerNorm input gradient of dy = a (+ b) at the rows x; one wave per row;
 //                                 leaves the summed dy in a and the row's (mean, rstd) for the column sums
-//   vcap_text_colsum_kernel       bias gradients: out[c] = sum_m src[m][c]; with the rows x and their stats:
+//   vcap_text_colsum_kernel       bias gradients: out[c] = sum_m src[m][c] (rows f32, or the decoder dtype for the
+//                                 GPT-2 tail's bias gradients: vcap_colsum_dispatch); with the rows x and their stats:
 //                                 dgamma[c] = sum_m dy[m][c] xhat[m][c] and dbeta[c] = sum_m dy[m][c]
 //   vcap_text_transpose_kernel    src [M][N] (f32 or T) -> dst [N][Mpad] in T through a 32 x 64 LDS tile, columns
 //                                 m >= M written as +0: the K-contiguous operands dY^T and X^T of
@@ -195,8 +196,10 @@ __global__ __launch_bounds__(256) void vcap_text_ln_bwd_kernel(const float* __re
 
 // grid N / 64, 256 threads: lane -> column, wave w -> rows w, w + 4, ... in order; the four partial sums are
 // added in wave order.  With x and stats: out = sum dy xhat (dgamma) and out2 = sum dy (dbeta); without: out =
-// sum src (a bias gradient).
-__global__ __launch_bounds__(256) void vcap_text_colsum_kernel(const float* __restrict__ src,
+// sum src (a bias gradient).  S: the rows' dtype (f32 here; the GPT-2 tail's bias gradients sum rows of the
+// decoder dtype, vcap_colsum_dispatch); the sums are f32.
+template <typename S>
+__global__ __launch_bounds__(256) void vcap_text_colsum_kernel(const S* __restrict__ src,
                                                                const float* __restrict__ x,
                                                                const float* __restrict__ stats, int M, int N,
                                                                float* __restrict__ out, float* __restrict__ out2) {
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(256) void vcap_text_colsum_kernel(const float* __re
   const int c = blockIdx.x * 64 + lane;
   float s = 0.f, sx = 0.f;
   for (int m = wave; m < M; m += 4) {
-    const float d = src[(long)m * N + c];
+    const float d = Num<S>::to_f(src[(long)m * N + c]);
     s += d;
     if (x) {
       const f32x2 st = *reinterpret_cast<const f32x2*>(stats + 2L * m);
@@ -403,15 +406,30 @@ hipError_t vcap_text_ln_bwd_dispatch(const float* x, float* a, const float* b, c
   if (M <= 0 || E <= 0 || E % 128 || E > 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(vcap_text_ln_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, a, b, gamma, eps, M, E, dx, stats);
   if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(vcap_text_colsum_kernel, dim3(E / 64), dim3(256), 0, s, (const float*)a, x, (const float*)stats,
-                     M, E, dgamma, dbeta);
+  return vcap_ln_colsum_dispatch(a, x, stats, M, E, dgamma, dbeta, s);
+}
+
+hipError_t vcap_ln_colsum_dispatch(const float* dy, const float* x, const float* stats, int M, int E, float* dgamma,
+                                   float* dbeta, hipStream_t s) {
+  if (M <= 0 || E <= 0 || E % 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(vcap_text_colsum_kernel<float>, dim3(E / 64), dim3(256), 0, s, dy, x, stats, M, E, dgamma, dbeta);
   return hipGetLastError();
 }
 
 hipError_t vcap_text_colsum_dispatch(const float* src, int M, int N, float* out, hipStream_t s) {
+  return vcap_colsum_dispatch(VCAP_DT_F32, src, M, N, out, s);
+}
+
+hipError_t vcap_colsum_dispatch(int dt, const void* src, int M, int N, float* out, hipStream_t s) {
   if (M <= 0 || N <= 0 || N % 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vcap_text_colsum_kernel, dim3(N / 64), dim3(256), 0, s, src, (const float*)nullptr,
-                     (const float*)nullptr, M, N, out, (float*)nullptr);
+  if (dt == VCAP_DT_F32)
+    hipLaunchKernelGGL(vcap_text_colsum_kernel<float>, dim3(N / 64), dim3(256), 0, s, (const float*)src,
+                       (const float*)nullptr, (const float*)nullptr, M, N, out, (float*)nullptr);
+  else if (dt == VCAP_DT_BF16)
+    hipLaunchKernelGGL(vcap_text_colsum_kernel<bf16_t>, dim3(N / 64), dim3(256), 0, s, (const bf16_t*)src,
+                       (const float*)nullptr, (const float*)nullptr, M, N, out, (float*)nullptr);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

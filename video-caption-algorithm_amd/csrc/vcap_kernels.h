@@ -225,6 +225,13 @@ hipError_t vcap_score_dlogit_dispatch(int dt, const float* part_max, const float
 // g [M, E] += the LayerNorm input gradient of dy at the rows x (gamma frozen)
 hipError_t vcap_ln_backward_dispatch(const float* x, const float* dy, const float* gamma, float eps, int M, int E,
                                      float* g, hipStream_t s);
+// the same update of g (same bits), plus stats [M][2] = each row's (mean, rstd) for vcap_ln_colsum_dispatch
+hipError_t vcap_ln_backward_stats_dispatch(const float* x, const float* dy, const float* gamma, float eps, int M,
+                                           int E, float* g, float* stats, hipStream_t s);
+// dW [K, N] f32 = X^T . dY over the M <= 512 rows of X [M, K] and dY [M, N] (dt); K % 64 == 0, N % 128 == 0
+// (gpt2_weight_grad.hip)
+hipError_t vcap_gpt2_dw_dispatch(int dt, const void* X, const void* dY, float* dW, int M, int K, int N,
+                                 hipStream_t s);
 hipError_t vcap_gelu_backward_dispatch(int dt, const float* u, const float* dact, long n, void* du, hipStream_t s);
 hipError_t vcap_grad_to_bf16_dispatch(const float* x, long n, void* y, hipStream_t s);
 // qkv [B*S, 3 * 64 H] f32, dO [B*S, 64 H] f32, kmask [B, S] or nullptr; P, dS: [B*H, S, S] f32 scratch;
@@ -365,6 +372,12 @@ hipError_t vcap_text_ln_bwd_dispatch(const float* x, float* a, const float* b, c
                                      int E, float* dx, float* stats, float* dgamma, float* dbeta, hipStream_t s);
 // out [N] = sum over the M rows of src [M, N] in a fixed order; N % 64 == 0
 hipError_t vcap_text_colsum_dispatch(const float* src, int M, int N, float* out, hipStream_t s);
+// the same sum over rows of dtype dt (f32 or bf16), f32 accumulation and output
+hipError_t vcap_colsum_dispatch(int dt, const void* src, int M, int N, float* out, hipStream_t s);
+// dgamma [E] = sum_m dy[m] xhat[m] and dbeta [E] = sum_m dy[m] in the column sum's order; xhat from the rows x
+// and their stats [M][2] = (mean, rstd)
+hipError_t vcap_ln_colsum_dispatch(const float* dy, const float* x, const float* stats, int M, int E, float* dgamma,
+                                   float* dbeta, hipStream_t s);
 // dst (dt) [N, Mpad] = src^T, src [M, N] f32 (src_f32) or dt; columns m >= M are +0; N % 64 == 0, Mpad % 32 == 0
 hipError_t vcap_text_transpose_dispatch(int dt, int src_f32, const void* src, int M, int N, int Mpad, void* dst,
                                         hipStream_t s);

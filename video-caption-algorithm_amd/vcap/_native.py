@@ -70,6 +70,15 @@ class GPT2GradDesc(C.Structure):
                 ("layers", C.POINTER(GPT2GradLayer))]
 
 
+class GPT2ParamGradsLayer(C.Structure):
+    _fields_ = [("ln1_g", vp), ("ln1_b", vp), ("attn_w", vp), ("attn_b", vp), ("aproj_w", vp), ("aproj_b", vp),
+                ("ln2_g", vp), ("ln2_b", vp), ("fc_w", vp), ("fc_b", vp), ("mproj_w", vp), ("mproj_b", vp)]
+
+
+class GPT2ParamGrads(C.Structure):
+    _fields_ = [("n_tail", i32), ("layers", C.POINTER(GPT2ParamGradsLayer))]
+
+
 class GenParams(C.Structure):
     _fields_ = [("max_new_tokens", i32), ("min_new_tokens", i32), ("no_repeat_ngram_size", i32),
                 ("repetition_penalty", f32), ("eos_token_id", i32), ("pad_token_id", i32), ("use_graph", i32),
@@ -176,6 +185,11 @@ SIGNATURES = {
     "vcap_gpt2_score_backward_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), i32, i32]),
     "vcap_gpt2_score_backward": (i32, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), vp, i32, i32, vp, vp, vp, vp, vp,
                                        vp, vp, sz, vp]),
+    "vcap_gpt2_score_backward_tail_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), i32, i32,
+                                                           i32]),
+    "vcap_gpt2_score_backward_tail": (i32, [C.POINTER(GPT2Desc), C.POINTER(GPT2GradDesc), vp, i32, i32, vp, vp, vp,
+                                            vp, C.POINTER(GPT2ParamGrads), vp, vp, vp, sz, vp]),
+    "vcap_gpt2_weight_grad": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
     "vcap_l2_normalize": (i32, [vp, i64, vp, i64, i32, i32, f32, i32, vp]),
     "vcap_ip_index_convert": (i32, [vp, i64, i32, i32, i32, vp, vp]),
     "vcap_ip_search_workspace_bytes": (sz, [i64, i32, i32, i32]),

@@ -314,15 +314,20 @@ class HipGPT2Decoder:
         dev = self.device
         p = "decoder.model.transformer."
         self._keep: List[torch.Tensor] = []
+        # state-dict name -> its device copy: the f32 tensor of a bias / LayerNorm affine, the rows-packed
+        # buffer of a Conv1D weight.  load_tail() rewrites these in place.
+        self._named: Dict[str, torch.Tensor] = {}
 
         def f32(k):
             t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).contiguous()
             self._keep.append(t)
+            self._named[k] = t
             return t
 
         def conv_t(k):  # Conv1D [in, out] -> [out, in] -> rows-packed (vcap_rows_pack)
             t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).t().contiguous()
-            return self._pack(t.to(dev).to(tdt).contiguous())
+            self._named[k] = self._pack(t.to(dev).to(tdt).contiguous())
+            return self._named[k]
 
         self.wte = torch.from_numpy(np.ascontiguousarray(sd[p + "wte.weight"], np.float32)).to(dev).to(tdt)
         self.wte = self.wte.contiguous()
@@ -367,10 +372,17 @@ class HipGPT2Decoder:
         if nbytes == 0:
             raise ValueError(f"cannot pack a [{rows}, {k}] weight (K must be a multiple of 32 bf16 / 16 f32)")
         packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        N.check(N.lib().vcap_rows_pack(dt, w.data_ptr(), w.stride(0), rows, k, packed.data_ptr(),
-                                       _stream(w.device)), "vcap_rows_pack")
+        self._pack_into(w, packed, dt)
         self._keep.append(packed)
         return packed
+
+    def _pack_into(self, w: torch.Tensor, packed: torch.Tensor, dt: Optional[int] = None) -> None:
+        dt = self.dt if dt is None else dt
+        rows, k = w.shape
+        if packed.numel() != int(N.lib().vcap_rows_packed_bytes(dt, rows, k)):
+            raise ValueError(f"packed buffer of {packed.numel()} bytes does not hold a [{rows}, {k}] weight")
+        N.check(N.lib().vcap_rows_pack(dt, w.data_ptr(), w.stride(0), rows, k, packed.data_ptr(),
+                                       _stream(w.device)), "vcap_rows_pack")
 
     def workspace_bytes(self, B: int, prompt_len: int, max_new: int) -> int:
         return int(N.lib().vcap_gpt2_workspace_bytes(C.byref(self.desc), B, self.prefix_len + prompt_len, max_new))
@@ -545,10 +557,15 @@ class HipGPT2Decoder:
         dev, tdt = self.device, _dtype(self.precision)[1]
         p = "decoder.model.transformer."
         keep: List[torch.Tensor] = []
+        # state-dict name of a Conv1D weight -> its [in, out] copy (and, for c_attn / c_fc, the Linear-layout
+        # one): what load_tail() rewrites
+        named: Dict[str, List[torch.Tensor]] = {}
 
-        def up(a: torch.Tensor) -> int:
+        def up(a: torch.Tensor, name: Optional[str] = None) -> int:
             t = a.to(dev).to(tdt).contiguous()
             keep.append(t)
+            if name is not None:
+                named.setdefault(name, []).append(t)
             return t.data_ptr()
 
         def mat(k):
@@ -562,11 +579,15 @@ class HipGPT2Decoder:
         for i in range(self.arch.n_layer):
             b = f"{p}h.{i}."
             ly = layers[i]
-            attn, fc = mat(b + "attn.c_attn.weight"), mat(b + "mlp.c_fc.weight")
-            ly.attn_c, ly.aproj_c = up(attn), up(mat(b + "attn.c_proj.weight"))
-            ly.fc_c, ly.mproj_c = up(fc), up(mat(b + "mlp.c_proj.weight"))
-            ly.attn_l, ly.fc_l = up(attn.t()), up(fc.t())
+            na, nf = b + "attn.c_attn.weight", b + "mlp.c_fc.weight"
+            attn, fc = mat(na), mat(nf)
+            ly.attn_c = up(attn, na)
+            ly.aproj_c = up(mat(b + "attn.c_proj.weight"), b + "attn.c_proj.weight")
+            ly.fc_c = up(fc, nf)
+            ly.mproj_c = up(mat(b + "mlp.c_proj.weight"), b + "mlp.c_proj.weight")
+            ly.attn_l, ly.fc_l = up(attn.t(), na), up(fc.t(), nf)
         self._grad_layers = layers
+        self._grad_named = named
         self.grad_desc = N.GPT2GradDesc(dtype=self.dt, n_embd=E, n_layer=self.arch.n_layer, vocab_pad=vpad,
                                         wte_t=up(wte_t), layers=layers)
         self._grad_keep = keep
@@ -584,17 +605,53 @@ class HipGPT2Decoder:
         chunks.  A sequence's gradient bits do not depend on the other sequences of its call, so the chunked
         result equals the one-call bits.  Needs enable_grad(sd) first.  Returns (ScoreResult without
         logits, grad_embeds); logprobs and the loss pair are score()'s bits."""
+        res, grad, _ = self._score_backward("score_backward", embeds, key_mask, targets, grad_logprob, check_mask, 0)
+        return res, grad
+
+    TAIL_PARAMS = ("ln_1.weight", "ln_1.bias", "attn.c_attn.weight", "attn.c_attn.bias", "attn.c_proj.weight",
+                   "attn.c_proj.bias", "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias",
+                   "mlp.c_proj.weight", "mlp.c_proj.bias")   # vcap_gpt2_param_grads_layer's field order
+
+    def tail_names(self, n_tail: int) -> List[str]:
+        """State-dict names of every parameter of the last n_tail blocks, layer by layer in TAIL_PARAMS order."""
+        L = self.arch.n_layer
+        if not 1 <= int(n_tail) <= L:
+            raise N.VcapError(f"n_tail = {n_tail} outside 1 .. n_layer = {L}", N.E_ARG)
+        return [f"decoder.model.transformer.h.{i}.{k}" for i in range(L - int(n_tail), L) for k in self.TAIL_PARAMS]
+
+    def _tail_shape(self, name: str) -> Tuple[int, ...]:
+        E = self.arch.n_embd
+        mod, kind = name.split(".", 5)[5].rsplit(".", 1)   # "attn.c_attn", "weight"
+        fan_in, fan_out = {"attn.c_attn": (E, 3 * E), "attn.c_proj": (E, E), "mlp.c_fc": (E, 4 * E),
+                           "mlp.c_proj": (4 * E, E)}.get(mod, (E, E))
+        return (fan_in, fan_out) if kind == "weight" and not mod.startswith("ln_") else (fan_out,)
+
+    @torch.no_grad()
+    def score_backward_tail(self, embeds: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
+                            targets: Optional[torch.Tensor] = None, grad_logprob: Optional[torch.Tensor] = None,
+                            n_tail: int = 1, check_mask: bool = True
+                            ) -> Tuple["ScoreResult", torch.Tensor, Dict[str, torch.Tensor]]:
+        """score_backward plus the gradient of the same objective with respect to every parameter of the last
+        n_tail blocks (vcap_gpt2_score_backward_tail): {state-dict name: f32 device tensor in HF's layout}.
+        The ScoreResult and grad_embeds are score_backward's bits.  Chunked as score_backward chunks; the
+        chunks' parameter gradients are added in chunk order."""
+        names = self.tail_names(n_tail)
+        res, grad, pg = self._score_backward("score_backward_tail", embeds, key_mask, targets, grad_logprob,
+                                             check_mask, int(n_tail))
+        return res, grad, dict(zip(names, pg))
+
+    def _score_backward(self, who: str, embeds, key_mask, targets, grad_logprob, check_mask: bool, n_tail: int):
         if getattr(self, "grad_desc", None) is None:
-            raise N.VcapError("score_backward: call enable_grad(sd) first", N.E_ARG)
+            raise N.VcapError(f"{who}: call enable_grad(sd) first", N.E_ARG)
         if targets is None:
-            raise ValueError("score_backward: targets are required")
+            raise ValueError(f"{who}: targets are required")
         x = embeds.to(self.device, torch.float32).contiguous()
         if x.dim() != 3 or x.shape[2] != self.arch.n_embd:
             raise ValueError(f"embeds shape {tuple(x.shape)} != [B, S, {self.arch.n_embd}]")
         B, S, _ = x.shape
         max_rows = int(N.lib().vcap_gpt2_max_rows())
         if B < 1 or S < 1 or S > max_rows or S > self.arch.n_positions:
-            raise N.VcapError(f"score_backward: S = {S} exceeds vcap_gpt2_max_rows() = {max_rows} or n_positions",
+            raise N.VcapError(f"{who}: S = {S} exceeds vcap_gpt2_max_rows() = {max_rows} or n_positions",
                               N.E_UNSUPPORTED)
         km = gw = None
         if key_mask is not None:
@@ -602,8 +659,7 @@ class HipGPT2Decoder:
             if tuple(km.shape) != (B, S):
                 raise ValueError(f"key_mask shape {tuple(km.shape)} != {(B, S)}")
             if check_mask and not bool(km[:, 0].all()):
-                raise N.VcapError("score_backward: key_mask[:, 0] must be nonzero (a row with no visible key)",
-                                  N.E_ARG)
+                raise N.VcapError(f"{who}: key_mask[:, 0] must be nonzero (a row with no visible key)", N.E_ARG)
         tg = targets.to(self.device, torch.int32).contiguous()
         if tuple(tg.shape) != (B, S):
             raise ValueError(f"targets shape {tuple(tg.shape)} != {(B, S)}")
@@ -618,19 +674,62 @@ class HipGPT2Decoder:
         pairs = torch.empty(len(starts), 2, dtype=torch.float32, device=self.device)
         stream = _stream(self.device)
         lib = N.lib()
+        total = None   # the tail call: the chunks' parameter gradients, added in chunk order
+        if n_tail:
+            shapes = [self._tail_shape(k) for k in self.tail_names(n_tail)]
+            per_layer = len(self.TAIL_PARAMS)
         for ci, b0 in enumerate(starts):
             nb = min(per, B - b0)
-            ws = self.ws.get(int(lib.vcap_gpt2_score_backward_workspace_bytes(C.byref(self.desc),
-                                                                              C.byref(self.grad_desc), nb, S)))
-            N.check(lib.vcap_gpt2_score_backward(C.byref(self.desc), C.byref(self.grad_desc), x[b0:].data_ptr(), nb, S,
-                                                 N.ptr(None if km is None else km[b0:]), tg[b0:].data_ptr(),
-                                                 N.ptr(None if gw is None else gw[b0:]), grad[b0:].data_ptr(),
-                                                 logprobs[b0:].data_ptr(), pairs[ci].data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), stream), "vcap_gpt2_score_backward")
+            args = (x[b0:].data_ptr(), nb, S, N.ptr(None if km is None else km[b0:]), tg[b0:].data_ptr(),
+                    N.ptr(None if gw is None else gw[b0:]), grad[b0:].data_ptr())
+            outs = (logprobs[b0:].data_ptr(), pairs[ci].data_ptr())
+            if not n_tail:
+                ws = self.ws.get(int(lib.vcap_gpt2_score_backward_workspace_bytes(C.byref(self.desc),
+                                                                                  C.byref(self.grad_desc), nb, S)))
+                N.check(lib.vcap_gpt2_score_backward(C.byref(self.desc), C.byref(self.grad_desc), *args, *outs,
+                                                     ws.data_ptr(), ws.numel(), stream), "vcap_gpt2_score_backward")
+                continue
+            pgs = [torch.empty(sh, dtype=torch.float32, device=self.device) for sh in shapes]
+            layers = (N.GPT2ParamGradsLayer * n_tail)()
+            for i in range(n_tail):
+                for j, (field, _) in enumerate(N.GPT2ParamGradsLayer._fields_):
+                    setattr(layers[i], field, pgs[i * per_layer + j].data_ptr())
+            pg = N.GPT2ParamGrads(n_tail=n_tail, layers=layers)
+            ws = self.ws.get(int(lib.vcap_gpt2_score_backward_tail_workspace_bytes(
+                C.byref(self.desc), C.byref(self.grad_desc), nb, S, n_tail)))
+            N.check(lib.vcap_gpt2_score_backward_tail(C.byref(self.desc), C.byref(self.grad_desc), *args, C.byref(pg),
+                                                      *outs, ws.data_ptr(), ws.numel(), stream),
+                    "vcap_gpt2_score_backward_tail")
+            total = pgs if total is None else [a + b for a, b in zip(total, pgs)]
         nll_sum, count = pairs[0, 0], pairs[0, 1]
         for ci in range(1, len(starts)):   # chunk order, as score()
             nll_sum, count = nll_sum + pairs[ci, 0], count + pairs[ci, 1]
-        return ScoreResult(None, logprobs, nll_sum, count), grad
+        return ScoreResult(None, logprobs, nll_sum, count), grad, total
+
+    @torch.no_grad()
+    def load_tail(self, state: Dict[str, torch.Tensor]) -> None:
+        """Rewrite, in place, every device copy of the transformer-block parameters named in `state`
+        (decoder.model.transformer.h.{i}.*, f32 values in HF's layouts; other keys are ignored): the
+        rows-packed forward weights (vcap_rows_pack into the same buffers), the f32 biases and LayerNorm
+        affines, and - after enable_grad - the grad desc's Conv1D and Linear-layout copies.  No pointer in
+        desc, layers or grad_desc changes, so captured decode graphs stay valid and replay with the new
+        weights.  A bf16 decoder stores the RNE rounding of the f32 values, as __init__ does."""
+        tdt = _dtype(self.precision)[1]
+        grad_named = getattr(self, "_grad_named", {})
+        prefix = "decoder.model.transformer.h."
+        for name, v in state.items():
+            if not name.startswith(prefix) or name not in self._named:
+                continue
+            v = torch.as_tensor(v).detach().to(self.device, torch.float32)
+            if name.endswith(".weight") and v.dim() == 2:   # Conv1D [in, out]
+                self._pack_into(v.t().contiguous().to(tdt).contiguous(), self._named[name])
+                for t, src in zip(grad_named.get(name, []), (v, v.t())):   # [in, out], then [out, in]
+                    t.copy_(src.to(tdt))
+            else:
+                if tuple(v.shape) != tuple(self._named[name].shape):
+                    raise ValueError(f"{name}: shape {tuple(v.shape)} != {tuple(self._named[name].shape)}")
+                self._named[name].copy_(v)
+        torch.cuda.synchronize(self.device)   # the copies ran on the current stream; decodes may use others
 
     def _beam_ids(self, prefix, prompt_ids, cfg: GenConfig, out, workspace, lengths_out):
         B, P, E = prefix.shape
