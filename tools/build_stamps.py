@@ -3,7 +3,9 @@
 A-fragment barrier), MFMAs retired (split-K partials written), reduction barrier passed, epilogue
 issued.  The product sources are not touched: this script patches a copy under /tmp and builds
 video-caption-algorithm_amd/vcap/_lib/libvcap_stamps.so (use it with VCAP_LIB=..., read with
-tools/decode_stamps.py).  Stamps go to a __device__ buffer that nothing else reads.
+tools/decode_stamps.py, tools/attn_stamps.py, tools/gemm_stamps.py).  Stamps go to a __device__ buffer
+that nothing else reads.
+usage: build_stamps.py [--src <csrc directory of another checkout>] [--out <library file name>]
 """
 import os
 import re
@@ -131,7 +133,38 @@ def patch_attention(s: str) -> str:
     return s[:k0] + b + s[k1:]
 
 
+def patch_gemm256(s: str) -> str:
+    # 256x256 ViT GEMM, every instance (tag 0xD000 | EPI): entry | first K-tile landed | K loop done |
+    # epilogue issued | its loads and stores complete | HW_ID and XCC_ID of the workgroup's CU
+    s = s.replace('#include "vcap_kernels.h"\n', '#include "vcap_kernels.h"\n' + header("_g256"), 1)
+    k0 = s.index("void vcap_gemm256_kernel(")
+    k1 = s.index("static hipError_t launch256_epi(")
+    k1 = s.rindex("}", k0, k1)
+    b = s[k0:k1]
+    b = b.replace("  extern __shared__ __attribute__((aligned(16))) char smem[];\n",
+                  "  extern __shared__ __attribute__((aligned(16))) char smem[];\n"
+                  "  const unsigned long long st0 = VCAP_RT();\n", 1)
+    b = b.replace("  wait_landed();\n  end_phase();\n", "  wait_landed();\n  end_phase();\n"
+                  "  const unsigned long long st1 = VCAP_RT();\n", 1)
+    b = b.replace("  if constexpr (MX) mfma_mx_drain();\n", "  if constexpr (MX) mfma_mx_drain();\n"
+                  "  const unsigned long long st2 = VCAP_RT();\n", 1)
+    b += ("  const unsigned long long st3 = VCAP_RT();\n"
+          "  asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+          "  const unsigned long long st4 = VCAP_RT();\n"
+          "  if (threadIdx.x == 0)\n"
+          "    vcap_stamp_rec_g256(0xD000ull | EPI, st0, st1, st2, st3, st4, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |\n"
+          "                        ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32));\n")
+    assert b.count("VCAP_RT()") == 5, b.count("VCAP_RT()")
+    return s[:k0] + b + s[k1:]
+
+
 def main():
+    global SRC, OUT
+    args = sys.argv[1:]
+    if "--src" in args:
+        SRC = Path(args[args.index("--src") + 1]).resolve()
+    if "--out" in args:
+        OUT = OUT.with_name(args[args.index("--out") + 1])
     tmp = Path("/tmp/vcap_stamps_build")
     shutil.rmtree(tmp, ignore_errors=True)
     src = tmp / "pkg" / "csrc"  # runtime_common.h includes ../../include/vcap.h
@@ -146,6 +179,8 @@ def main():
     p.write_text(patch_decode_attention(p.read_text()))
     p = src / "vit_attention.hip"
     p.write_text(patch_attention(p.read_text()))
+    p = src / "gemm256.hip"
+    p.write_text(patch_gemm256(p.read_text()))
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-Wno-unused-result",
              f"-I{src}", f"-I{ROOT / 'include'}"]
     procs = []

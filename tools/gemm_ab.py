@@ -1,6 +1,6 @@
 """Interleaved A/B timing of the ViT GEMM shapes across library builds / GEMM policies in ONE
-process (box-to-box clock differences cancel).  usage: gemm_ab.py [M] lib.so:policy ...
-('-' as the library = the in-tree build)."""
+process (box-to-box clock differences cancel).  usage: gemm_ab.py [M] [--f16] lib.so:policy ...
+('-' as the library = the in-tree build; --f16: f16 operands instead of bf16)."""
 import ctypes as C
 import statistics
 import sys
@@ -24,11 +24,12 @@ for a in args:
     variants.append((a, h, int(pol)))
 
 dev = torch.device("cuda:0")
+OP_T, OP_DT = (torch.float16, N.DT_F16) if "--f16" in sys.argv else (torch.bfloat16, N.DT_BF16)
 s = torch.cuda.current_stream().cuda_stream
 g = torch.Generator(device=dev).manual_seed(0)
 
 
-def rnd(*shape, scale=1.0, dtype=torch.bfloat16):
+def rnd(*shape, scale=1.0, dtype=OP_T):
     return (torch.rand(*shape, generator=g, device=dev) * 2 - 1).mul_(scale).to(dtype)
 
 
@@ -39,14 +40,14 @@ if "--with-nogelu" in sys.argv:
 bufs = {}
 for name, (n, k, f32, act) in shapes.items():
     bufs[name] = (rnd(M, k), rnd(n, k, scale=0.05), rnd(n, scale=0.1, dtype=torch.float32),
-                  torch.zeros(M, n, device=dev, dtype=torch.float32 if f32 else torch.bfloat16))
+                  torch.zeros(M, n, device=dev, dtype=torch.float32 if f32 else OP_T))
 
 
 def run(h, name, reps):
     n, k, f32, act = shapes[name]
     A, W, b, Cc = bufs[name]
     for _ in range(reps):
-        rc = h.vcap_gemm(N.DT_BF16, N.DT_F32 if f32 else N.DT_BF16, A.data_ptr(), k, W.data_ptr(), k, Cc.data_ptr(),
+        rc = h.vcap_gemm(OP_DT, N.DT_F32 if f32 else OP_DT, A.data_ptr(), k, W.data_ptr(), k, Cc.data_ptr(),
                          n, M, n, k, b.data_ptr(), act, Cc.data_ptr() if f32 else None, n if f32 else 0,
                          1 if f32 else 0, 0, 0, 0, 0, s)
         if rc:

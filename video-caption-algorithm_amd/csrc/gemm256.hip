@@ -24,7 +24,10 @@
 //    a staged buffer is read only in a phase after the counted wait and the barrier that
 //    follow it in both groups;
 //  * the MFMA takes the weight fragment as its A operand, so each lane ends up holding 4
-//    consecutive output COLUMNS of one row: vectorised bias / residual / store epilogue.
+//    consecutive output COLUMNS of one row: vectorised bias / residual / store epilogue;
+//  * the in-place f32 residual (EPI == 2) is fetched under the tail of the K loop: the last iteration
+//    stages nothing, so its slots issue the residual tile by LDS-DMA into the halves of the last two
+//    K-tiles as each is read for the last time, and into the LDS no K-tile uses (ResPieces below).
 #include <cstdlib>
 
 #include "vcap_common.h"
@@ -69,7 +72,13 @@ VCAP_DEV void glds4(const void* g, char* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
 
+// PIN: the uniform base is taken through an opaque scalar copy, so every load keeps the SGPR-base +
+// 32-bit-VGPR-offset form.  Left alone the compiler folds base + offset into a 64-bit register pair per
+// staged piece, kept across the K loop: 8 registers more, with which the EPI == 2 instance (which also
+// prefetches its residual there) spills.
+template <bool PIN = false>
 VCAP_DEV void stage_half(const char* base_k, const uint32_t (&off)[2], char* lds_half, int wave) {
+  if constexpr (PIN) asm volatile("" : "+s"(base_k));
 #pragma unroll
   for (int i = 0; i < 2; ++i) glds16(base_k + off[i], lds_half + (wave * 2 + i) * 1024);
 }
@@ -96,6 +105,78 @@ VCAP_DEV uint32_t pack_out2(float lo, float hi) {
 }
 
 VCAP_DEV void lds_fence() { asm volatile("" ::: "memory"); }
+VCAP_DEV int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// In-place f32 residual (EPI == 2) with 16-bit operands (kResPrefetch; f32 and MXFP8 operands keep the
+// register epilogue: not timed, profiles/residual_prefetch_ab.txt).  A wave's 128 x 64 residual block is 32
+// pieces, one per 16x16 MFMA tile (1 KiB: lane (fr, fg) holds res[m + fr][n + 4 fg .. + 3], the accumulator's
+// own layout), numbered in the epilogue's store order: piece p is tile (i, j) = ((p >> 1) & 3, p & 1) of
+// quadrant (qm, qn) = (p >> 4, (p >> 3) & 1).  Pieces 0 .. kLds-1 are fetched by LDS-DMA in the last
+// iteration of the K loop, whose staging slots are vacant; a 16-byte LDS-DMA lands lane-linear, so the lane
+// that issued a piece reads it back at slot + lane * 16 and no wave reads another wave's slot:
+//   pieces 0 .. 7     the wave's 2 KiB of each half of K-tile nk-2 (buffer 0: nk is even), one half per
+//                     slot in the order the halves are read for the last time
+//   pieces 8 .. 11    the 32 KiB of LDS above the K-tile buffers, free all launch
+//   pieces 12 .. 19   the halves of K-tile nk-1 (buffer 1), the same way
+// and pieces 20 .. 31 by plain loads after the loop, into the registers the fragments leave.
+template <typename TIn, int EPI>
+constexpr bool kResPrefetch = EPI == 2 && sizeof(TIn) == 2;
+struct ResPieces {
+  static constexpr int kSpare = 4, kLds = 16 + kSpare, kReg = 32 - kLds;
+  static constexpr int kLdsBytes = LDS_BYTES + 8 * kSpare * 1024;  // 160 KiB
+};
+
+VCAP_DEV char* res_piece_lds(char* smem, int p, int wave) {
+  using R = ResPieces;
+  if (p >= 8 && p < 8 + R::kSpare) return smem + LDS_BYTES + (wave * R::kSpare + p - 8) * 1024;
+  const int q = p < 8 ? p : p - 8 - R::kSpare;
+  const int s = q >> 1;                            // slot order A-h0, B-h0, B-h1, A-h1
+  const int h = s == 0 ? 0 : s == 3 ? 1 : s + 1;   // -> position in the buffer (A-h0 A-h1 B-h0 B-h1)
+  return smem + (p < 8 ? 0 : BUF) + h * HALF + (wave * 2 + (q & 1)) * 1024;
+}
+
+// Only tiles that lie wholly inside the matrix prefetch (res_prefetch_tile): no row or column is then
+// clamped, so a piece's address is affine - a uniform base (the wave's first residual element plus the
+// piece's own offset, scalar arithmetic) and ONE 32-bit lane offset shared by all 32 pieces - which is
+// what keeps the K loop inside its register budget.  An edge tile keeps epilogue256's register path.
+VCAP_DEV bool res_prefetch_tile(int m0, int n0, int M, int N) { return m0 + TM <= M && n0 + TN <= N; }
+VCAP_DEV const char* res_wave_base(const GemmEpi& epi, int m0, int n0, int wr, int wc) {
+  return reinterpret_cast<const char*>(epi.res + (long)(m0 + wr * 128) * epi.ldr + n0 + wc * 64);
+}
+VCAP_DEV long res_piece_off(int p, long ldr) {
+  return ((long)((p >> 4) * 64 + ((p >> 1) & 3) * 16) * ldr + ((p >> 3) & 1) * 32 + (p & 1) * 16) * 4;
+}
+VCAP_DEV uint32_t res_lane_off(int lane, long ldr) { return (uint32_t)((lane & 15) * (int)ldr + (lane >> 4) * 4) * 4u; }
+constexpr long kResMaxLd = 1L << 24;  // 15 rows * ldr * 4 bytes stays below 2^31
+
+// What the K loop's last iteration needs to stage a wave's pieces; on = the tile prefetches.
+struct ResStage {
+  char* smem;
+  const char* base;  // res_wave_base
+  long ldr;
+  uint32_t lo;       // res_lane_off
+  int wave;
+  bool on;
+  // pieces [p0, p1) by LDS-DMA
+  VCAP_DEV void operator()(int p0, int p1) const {
+    if (!on) return;
+    const char* b = base;
+    asm volatile("" : "+s"(b));  // (as stage_half's PIN: the 20 piece addresses are not formed outside the loop)
+#pragma unroll
+    for (int p = p0; p < p1; ++p) glds16(b + res_piece_off(p, ldr) + lo, res_piece_lds(smem, p, wave));
+  }
+};
+
+// A counted wait the compiler sees (the K loop's own waits are inline asm, which it does not): it takes
+// every load older than the last N as landed.  Without one, all LDS-DMA since the kernel's start stay
+// pending in its books, and it waits vmcnt(0) at the first use of any plain load and before it overwrites
+// a register that addressed one of them.
+template <int N>
+VCAP_DEV void wait_vm_seen() {
+  lds_fence();
+  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));  // vmcnt(N) alone
+  lds_fence();
+}
 
 }  // namespace
 
@@ -295,6 +376,48 @@ VCAP_DEV void epilogue256(const f32x4 (&acc)[2][2][4][2], int m0, int n0, int wr
   }
 }
 
+// In-place f32 residual epilogue of a tile whose residual the K loop prefetched (ResPieces; the tile has no
+// edge): C += acc + bias, in the store order and with the arithmetic of epilogue256's EPI == 2 branch.
+// The bias and the last kReg pieces are loaded here by plain loads, behind the LDS-DMA, so every load of
+// the tile is in flight before the first store.  vmcnt retires in order: the one explicit wait,
+// vmcnt(kReg), leaves only the kReg register pieces out, so the bias and every LDS piece have landed; the
+// compiler sees it and counts the register pieces against the stores from there on.
+template <typename TIn>
+VCAP_DEV void epilogue256_prefetched(const f32x4 (&acc)[2][2][4][2], const char* smem, int m0, int n0, int wr, int wc,
+                                     int wave, int lane, uint32_t lo, float* C, long ldc, const GemmEpi& epi) {
+  using R = ResPieces;
+  const char* rbase = res_wave_base(epi, m0, n0, wr, wc);
+  // no bias: the four loads still run, on the residual's first row, and are dropped after the wait (a load
+  // under a branch of its own makes the compiler wait for it there, with everything before it)
+  const float* bsrc = (epi.bias ? epi.bias : epi.res) + n0 + wc * 64 + (lane >> 4) * 4;
+  f32x4 bias[2][2], rr[R::kReg];
+#pragma unroll
+  for (int qn = 0; qn < 2; ++qn)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bias[qn][j] = *reinterpret_cast<const f32x4*>(bsrc + qn * 32 + j * 16);
+#pragma unroll
+  for (int k = 0; k < R::kReg; ++k)
+    rr[k] = *reinterpret_cast<const f32x4*>(rbase + res_piece_off(R::kLds + k, epi.ldr) + lo);
+  wait_vm_seen<R::kReg>();
+  if (!epi.bias) {
+#pragma unroll
+    for (int qn = 0; qn < 2; ++qn)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bias[qn][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  float* cw = C + (long)(m0 + wr * 128 + (lane & 15)) * ldc + n0 + wc * 64 + (lane >> 4) * 4;
+  auto store = [&](int p, const f32x4& r) {
+    const int qm = p >> 4, qn = (p >> 3) & 1, i = (p >> 1) & 3, j = p & 1;
+    const f32x4 v = Autocast<TIn>::rnd4(acc[qm][qn][i][j] + bias[qn][j]) + r;
+    out_store(reinterpret_cast<f32x4*>(cw + (long)(qm * 64 + i * 16) * ldc + qn * 32 + j * 16), v);
+  };
+#pragma unroll
+  for (int p = 0; p < R::kLds; ++p)
+    store(p, *reinterpret_cast<const f32x4*>(res_piece_lds(const_cast<char*>(smem), p, wave) + lane * 16));
+#pragma unroll
+  for (int k = 0; k < R::kReg; ++k) store(R::kLds + k, rr[k]);
+}
+
 template <typename TIn, typename TOut, int EPI>
 __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict__ A, long lda,
                                                            const TIn* __restrict__ W, long ldw, TOut* C, long ldc,
@@ -302,6 +425,7 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BK = ROWB / sizeof(TIn);
   constexpr bool MX = sizeof(TIn) == 1;  // MXFP8: one scaled 16x16x128 MFMA per K-tile and fragment
+  constexpr bool PF = kResPrefetch<TIn, EPI>;
 
   const int tiles_n = (N + TN - 1) / TN;
   const int tiles_m = (M + TM - 1) / TM;
@@ -360,13 +484,13 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
   }
   char* const sbase = smem + 2 * BUF;
   auto stA = [&](int X, int kt) {
-    stage_half((const char*)A + (long)kt * ROWB, offA[X], smem + (kt & 1) * BUF + X * HALF, wave);
+    stage_half<PF>((const char*)A + (long)kt * ROWB, offA[X], smem + (kt & 1) * BUF + X * HALF, wave);
     if constexpr (MX) {
       if (X == 0) glds4(s_src + kt * s_stride + lane * 4, sbase + (kt & 3) * SBUF + wave * 256);
     }
   };
   auto stB = [&](int Y, int kt) {
-    stage_half((const char*)W + (long)kt * ROWB, offB[Y], smem + (kt & 1) * BUF + (2 + Y) * HALF, wave);
+    stage_half<PF>((const char*)W + (long)kt * ROWB, offB[Y], smem + (kt & 1) * BUF + (2 + Y) * HALF, wave);
   };
   // Lane group fg reads 16-byte chunks fg and 4 + fg of each row: bf16 / f32 feed them to the two
   // K sub-steps; MXFP8 feeds both to one scaled MFMA, whose operand layout is exactly that
@@ -452,6 +576,12 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
   };
 
   const int nk = K / BK;  // even, >= 2 (dispatcher)
+  // a prefetching instance, a tile with no edge: the last iteration's vacant slots stage residual pieces
+  constexpr int XS = ResPieces::kSpare;
+  ResStage stR{};
+  if constexpr (PF)
+    stR = ResStage{smem, res_wave_base(epi, m0, n0, wr, wc), epi.ldr, res_lane_off(lane, epi.ldr), wave,
+                   res_prefetch_tile(m0, n0, M, N)};
   // prologue: K-tile 0 complete; K-tile 1 minus its A-h1 in flight
   stA(0, 0);
   stA(1, 0);
@@ -473,18 +603,23 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
     rdA(a0, 0, t);
     rdS(t);
     stA(1, t + 1);
+    if constexpr (PF) {
+      if (!more) stR(8, 8 + XS);
+    }
     sync_reads();
     mma(acc[0][0], a0, 0, b0, 0);
     end_phase();
 
     rdB(b1, 1, t);
     if (more) stA(0, t + 2);
+    else if constexpr (PF) stR(0, 2);
     sync_reads();
     mma(acc[0][1], a0, 0, b1, 1);
     end_phase();
 
     rdA(a1, 1, t);
     if (more) stB(0, t + 2);
+    else if constexpr (PF) stR(2, 4);
     sync_reads();
     mma(acc[1][1], a1, 1, b1, 1);
     end_phase();
@@ -492,6 +627,9 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
     if (more) {
       stB(1, t + 2);
       wait_landed();  // K-tile t+1 landed (this wave's part)
+    } else if (stR.on) {
+      stR(4, 6);
+      wait_vm_seen<XS + 6>();  // K-tile t+1 landed: only this iteration's residual pieces are behind it
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -504,18 +642,21 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
     rdA(a0, 0, t + 1);
     rdS(t + 1);
     if (more) stA(1, t + 2);
+    else if constexpr (PF) stR(6, 8);
     sync_reads();
     mma(acc[0][0], a0, 0, b0, 0);
     end_phase();
 
     rdB(b1, 1, t + 1);
     if (more) stA(0, t + 3);
+    else if constexpr (PF) stR(8 + XS, 12 + XS);
     sync_reads();
     mma(acc[0][1], a0, 0, b1, 1);
     end_phase();
 
     rdA(a1, 1, t + 1);
     if (more) stB(0, t + 3);
+    else if constexpr (PF) stR(12 + XS, 14 + XS);
     sync_reads();
     mma(acc[1][1], a1, 1, b1, 1);
     end_phase();
@@ -523,6 +664,8 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
     if (more) {
       stB(1, t + 3);
       wait_landed();  // K-tile t+2 landed
+    } else if constexpr (PF) {
+      stR(14 + XS, 16 + XS);
     }
     sync_reads();
     mma(acc[1][0], a1, 1, b0, 0);
@@ -531,13 +674,20 @@ __global__ __launch_bounds__(512) void vcap_gemm256_kernel(const TIn* __restrict
   if (wr == 0) __builtin_amdgcn_s_barrier();
   if constexpr (MX) mfma_mx_drain();
 
-  epilogue256<TIn, TOut, EPI>(acc, m0, n0, wr, wc, lane, M, N, C, ldc, epi);
+  if constexpr (PF) {
+    // (the lane id is taken afresh: kept in a register across the K loop for the epilogue alone, it spills)
+    if (stR.on) epilogue256_prefetched<TIn>(acc, smem, m0, n0, wr, wc, wave, lane_id(), stR.lo, C, ldc, epi);
+    else epilogue256<TIn, TOut, EPI>(acc, m0, n0, wr, wc, lane_id(), M, N, C, ldc, epi);
+  } else {
+    epilogue256<TIn, TOut, EPI>(acc, m0, n0, wr, wc, lane, M, N, C, ldc, epi);
+  }
 }
 
 template <typename TIn, typename TOut, int EPI>
 static hipError_t launch256_epi(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N,
                                 int K, const GemmEpi& epi, hipStream_t s) {
-  constexpr int lds = sizeof(TIn) == 1 ? LDS_BYTES_MX : LDS_BYTES;
+  constexpr bool MX = sizeof(TIn) == 1;
+  constexpr int lds = kResPrefetch<TIn, EPI> ? ResPieces::kLdsBytes : MX ? LDS_BYTES_MX : LDS_BYTES;
   static bool configured = false;
   if (!configured) {
     hipError_t e = hipFuncSetAttribute((const void*)vcap_gemm256_kernel<TIn, TOut, EPI>,
@@ -583,7 +733,8 @@ static hipError_t launch256(const void* A, long lda, const void* W, long ldw, vo
         return launch256_epi<TIn, TOut, 1>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
     }
     if constexpr (sizeof(TOut) == 4) {
-      if (plain_rows && epi.res_mode == 1 && epi.act == 0 && epi.res == (const float*)C && epi.ldr == ldc)
+      if (plain_rows && epi.res_mode == 1 && epi.act == 0 && epi.res == (const float*)C && epi.ldr == ldc &&
+          epi.ldr < kResMaxLd)
         return launch256_epi<TIn, TOut, 2>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
     }
     return launch256_epi<TIn, TOut, 3>(A, lda, W, ldw, C, ldc, M, N, K, epi, s);
