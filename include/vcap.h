@@ -173,6 +173,14 @@ int vcap_stream_destroy(void* stream);
 /* ---- op-level entry points ---- */
 int vcap_linear_bias(int dtype, const void* x, const void* w, const float* b, void* y, int rows, int in_features,
                      int out_features, void* stream);
+/* C[orow(m)][n] = epilogue(sum_k A[m][k] W[n][k]): F32, BF16 or F16 operands, K a multiple of one 128-byte K-tile
+ * row.  Both kernels fetch the operands by 16-byte LDS-DMA, so A and W must be 16-byte aligned and lda, ldw whole
+ * 16-byte vectors (4 f32 / 8 bf16 or f16 elements); anything else is VCAP_E_UNSUPPORTED before any launch
+ * (vcap_gemm_splitk alike).  The 256x256-tile kernel is not used when (M - 1) * lda or (N - 1) * ldw reaches
+ * 2^32 bytes (its operand offsets are 32-bit): such a call runs the 128x128-tile kernel under every policy.
+ * C, bias and res need only their element's alignment: the epilogues reach them with plain global vector loads
+ * and stores, which rely on the device's unaligned access mode (the HSA default) below 16 bytes.  BF16 operands
+ * write BF16 or F32, F16 operands F16 or F32, F32 operands F32; another pair is VCAP_E_UNSUPPORTED. */
 int vcap_gemm(int in_dtype, int out_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
               int64_t ldc, int M, int N, int K, const float* bias, int act, const float* res, int64_t ldr,
               int res_mode, int G, int Gs, int goff, int roff, void* stream);

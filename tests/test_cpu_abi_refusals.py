@@ -12,7 +12,10 @@ vcap_vit_encode came with the encoder shape sweep (tests/encoder_shapes.py): sha
 the encode then failed on after its first launches (-hipErrorInvalidValue from "attention" / "head_prefix").  Those of
 vcap_vit_attention_mx came with the MXFP8 kernel sweep (tests/test_gpu_mx_sweep.py): 33..192 and 225..256 tokens
 used to come back from the dispatcher as -hipErrorInvalidValue ("invalid argument"), not as a documented code; the
-entry point now asks vcap_vit_attention_supported before the dispatcher."""
+entry point now asks vcap_vit_attention_supported before the dispatcher.  The rows of vcap_gemm / vcap_gemm_splitk came
+with the dense GEMM sweep (tests/test_gpu_gemm_sweep.py); "isnew" there: an operand dtype or an (operand, output) pair
+the dispatcher used to turn down as -hipErrorInvalidValue, and operands that are not 16-byte aligned with row strides in whole 16-byte vectors,
+which used to launch the 128x128 kernel's 16-byte LDS-DMA on misaligned addresses."""
 import ctypes as C
 
 import pytest
@@ -82,9 +85,14 @@ GOOD = {
     "vit_encode": dict(d=_vit, pd=None, frames=P, B=1, T=2, enc=P, prefix_out=None, ws=P, ws_bytes=BIG, stream=None),
     "vit_layer_fuses": dict(d=_vit, layer=0),
     "vit_attention_mx": dict(qkv=P, out=P, scales=P, frames=2, tokens=197, heads=4, stream=None),
+    "gemm": dict(in_dt=N.DT_BF16, out_dt=N.DT_F32, A=P, lda=128, W=P, ldw=128, C=P, ldc=16, M=4, N=16, K=128, bias=P,
+                 act=0, res=None, ldr=0, res_mode=0, G=0, Gs=0, goff=0, roff=0, stream=None),
+    "gemm_splitk": dict(in_dt=N.DT_BF16, A=P, lda=384, W=P, ldw=384, C=P, ldc=16, M=4, N=16, K=384, bias=P, G=0, Gs=0,
+                        ws=P, ws_bytes=BIG, splits=None, stream=None),
 }
 SYMBOL = {"decode_attention": "vcap_decode_attention", "vit_encode": "vcap_vit_encode",
-          "vit_layer_fuses": "vcap_vit_layer_fuses_qkv_attention", "vit_attention_mx": "vcap_vit_attention_mx"}
+          "vit_layer_fuses": "vcap_vit_layer_fuses_qkv_attention", "vit_attention_mx": "vcap_vit_attention_mx",
+          "gemm": "vcap_gemm", "gemm_splitk": "vcap_gemm_splitk"}
 
 # (entry point, the argument made bad, code, message, new?)   desc=/gp=/bp=/sp= give descriptor fields
 ROWS = [
@@ -176,6 +184,39 @@ ROWS = [
     ("vit_attention_mx", dict(heads=3), UNSUP, "vcap_vit_attention_mx: heads*64 must be a multiple of 256"),
     ("vit_attention_mx", dict(tokens=33), UNSUP, "vcap_vit_attention_mx: serves 1..32, 193..224 and 257..288 tokens", "isnew"),
     ("vit_attention_mx", dict(tokens=225), UNSUP, "vcap_vit_attention_mx: serves 1..32, 193..224 and 257..288 tokens", "isnew"),
+    ("gemm", dict(A=None), ARG, "vcap_gemm: bad arguments"),
+    ("gemm", dict(K=0), ARG, "vcap_gemm: bad arguments"),
+    ("gemm", dict(in_dt=N.DT_MXFP8), ARG, "vcap_gemm: operands must be VCAP_DT_F32, VCAP_DT_BF16 or VCAP_DT_F16", "isnew"),
+    ("gemm", dict(K=96, lda=96, ldw=96), UNSUP, "vcap_gemm: K must be a multiple of the K step"),
+    ("gemm", dict(in_dt=N.DT_F32, K=48), UNSUP, "vcap_gemm: K must be a multiple of the K step"),
+    ("gemm", dict(lda=132), UNSUP, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors", "isnew"),
+    ("gemm", dict(ldw=129), UNSUP, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors", "isnew"),
+    ("gemm", dict(in_dt=N.DT_F32, lda=130), UNSUP, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors",
+     "isnew"),
+    ("gemm", dict(A=P + 8), UNSUP, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors", "isnew"),
+    ("gemm", dict(W=P + 2), UNSUP, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors", "isnew"),
+    ("gemm", dict(res_mode=1), ARG, "vcap_gemm: residual pointer missing"),
+    ("gemm", dict(res=P, res_mode=2, ldr=16), ARG, "vcap_gemm: row group G must be > 0"),
+    ("gemm", dict(G=-1), ARG, "vcap_gemm: row group G must be > 0"),
+    ("gemm", dict(out_dt=N.DT_BF16, res=P, res_mode=1, ldr=16), UNSUP, "vcap_gemm: residual needs f32 output"),
+    ("gemm", dict(in_dt=N.DT_F16, out_dt=N.DT_BF16), UNSUP, "vcap_gemm: f16 operands write f16 or f32"),
+    ("gemm", dict(out_dt=N.DT_F16), UNSUP, "vcap_gemm: bf16 operands write bf16 or f32", "isnew"),
+    ("gemm", dict(out_dt=7), UNSUP, "vcap_gemm: bf16 operands write bf16 or f32", "isnew"),
+    ("gemm", dict(in_dt=N.DT_F32, out_dt=N.DT_BF16), UNSUP, "vcap_gemm: f32 operands write f32", "isnew"),
+    ("gemm", dict(in_dt=N.DT_F16, out_dt=7), UNSUP, "vcap_gemm: f16 operands write f16 or f32"),
+    ("gemm_splitk", dict(bias=None), ARG, "vcap_gemm_splitk: bad arguments"),
+    ("gemm_splitk", dict(G=4, Gs=3), ARG, "vcap_gemm_splitk: bad arguments"),
+    ("gemm_splitk", dict(in_dt=N.DT_F32), ARG, "vcap_gemm_splitk: operands must be VCAP_DT_BF16 or VCAP_DT_F16"),
+    ("gemm_splitk", dict(K=100), UNSUP, "vcap_gemm_splitk: K must be a multiple of 64"),
+    ("gemm_splitk", dict(lda=388), UNSUP, "vcap_gemm_splitk: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors",
+     "isnew"),
+    ("gemm_splitk", dict(W=P + 4), UNSUP, "vcap_gemm_splitk: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors",
+     "isnew"),
+    ("gemm_splitk", dict(N=18, ldc=18), UNSUP,
+     "vcap_gemm_splitk: N, ldc in whole 16-byte vectors; C and workspace 16-byte aligned"),
+    ("gemm_splitk", dict(C=P + 4), UNSUP,
+     "vcap_gemm_splitk: N, ldc in whole 16-byte vectors; C and workspace 16-byte aligned"),
+    ("gemm_splitk", dict(ws_bytes=8 * 4 * 16 * 4 - 4), WS, "vcap_gemm_splitk: workspace < 8*M*N*4 bytes"),
 ]
 
 

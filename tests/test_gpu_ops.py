@@ -180,8 +180,12 @@ def test_abi_errors_are_reported(device):
 
 @pytest.mark.parametrize("M,K", [(25216, 768), (25216, 3072), (20000, 3072)])
 def test_gemm_inplace_residual_auto_policy(device, M, K):
-    """attn-proj / fc2 shapes under the auto policy: whole 256x256 rounds plus the split-K
-    remainder (partials + reduce) - bf16 operands, f32 residual stream updated in place."""
+    """attn-proj / fc2 shapes under the auto policy - bf16 operands, f32 residual stream updated in place.
+    On 256 CUs, 25216 rows are 297 tiles of 256x256: one whole round (rows [0, 21760)) on the 256x256 kernel
+    and the remaining 3456 rows on the 128x128 kernel, unsplit (vcap_gemm passes no partials workspace, so
+    gemm_splits never splits here); 20000 rows are 237 tiles, fewer than the CUs: the 128x128 kernel alone.
+    The split depends on the device's CU count; tests/test_gpu_gemm_sweep.py pins the row split on a stream
+    of 16 CUs against an exact oracle."""
     N_ = 768
     N.check(N.lib().vcap_set_gemm_policy(0), "policy")
     A = _rand((M, K), 21).to(torch.bfloat16)

@@ -59,7 +59,10 @@ __global__ __launch_bounds__(256) void vcap_gemm_kernel(const TIn* __restrict__ 
   tile_loop(A, lda, W, ldw, m0, M, n0, N, kt0, nk, smem, acc);
   const int fr = lane & 15, fg = lane >> 4;
 
-  // epilogue: lane holds row fr, columns 4*fg .. 4*fg+3 of each 16x16 tile
+  // epilogue: lane holds row fr, columns 4*fg .. 4*fg+3 of each 16x16 tile.  The vector branch asks for whole
+  // 16-byte vectors per row (N, ldc, ldr), not for 16-byte aligned C / residual pointers: its f32x4 / u32x2
+  // accesses are plain global loads and stores, which the device serves at the element's alignment (unaligned
+  // access mode, the HSA default; only the operands' LDS-DMA needs 16 bytes - vcap_gemm checks those).
   const bool vec = (N & 3) == 0 && (ldc & 3) == 0 && (!epi.res || (epi.ldr & 3) == 0);
   // in-place residual (EPI 2): every residual row of the wave is loaded before the first store
   // (load / add / store per element serialised 16 HBM round trips: the loads cannot pass the

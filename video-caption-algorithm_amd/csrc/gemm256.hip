@@ -742,7 +742,10 @@ static hipError_t launch256(const void* A, long lda, const void* W, long ldw, vo
 }
 
 // Shapes this kernel takes: K a multiple of two K-tiles, N and the strides in whole 16-byte
-// vectors for the epilogue, 16-byte aligned bias / residual rows.
+// vectors for the epilogue, 16-byte aligned bias / residual rows, and operand panels whose byte offsets
+// fit half_offsets' 32 bits (the last row's last chunk of a K-tile; the K-tile advance is on the 64-bit
+// base).  A wider row stride goes to the 128x128 kernel, which addresses with long (as kResMaxLd does
+// for the residual side: a wrapped offset would read another row of the same allocation, not fault).
 bool vcap_gemm256_ok(int in_dt, int out_dt, long lda, long ldw, long ldc, int M, int N, int K, const GemmEpi& epi) {
   if (!vcap_dt_size(in_dt) || !vcap_dt_size(out_dt)) return false;
   const int bk = 128 / (int)vcap_dt_size(in_dt);  // one 128-byte K-tile row
@@ -753,6 +756,10 @@ bool vcap_gemm256_ok(int in_dt, int out_dt, long lda, long ldw, long ldc, int M,
                                   !epi.c_scale || epi.G || epi.res_mode))
     return false;
   if (lda % ein || ldw % ein) return false;
+  // largest lane offset: (rows - 1) * ld * sizeof(T) + 112, the 16 bytes read there ending below 2^32 (the
+  // comparison divides, so a caller's huge stride cannot overflow it)
+  const long span = ((1L << 32) - 128) / (long)vcap_dt_size(in_dt);
+  if (lda < 0 || ldw < 0 || (M > 1 && lda > span / (M - 1)) || (N > 1 && ldw > span / (N - 1))) return false;
   if (ldc % 4) return false;
   if (epi.bias && ((uintptr_t)epi.bias & 15)) return false;
   if (epi.res && (((uintptr_t)epi.res & 15) || epi.ldr % 4)) return false;

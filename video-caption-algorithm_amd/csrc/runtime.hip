@@ -115,16 +115,32 @@ int vcap_set_gemm_policy(int policy) {
   return 0;
 }
 
+// Both GEMM kernels fetch their operands by 16-byte LDS-DMA (global_load_lds_dwordx4) from A + row * lda + 16-byte
+// chunk: every such address is 16-byte aligned exactly when the base is and the row stride is a whole number of
+// 16-byte vectors.  A misaligned LDS-DMA source is not something the ISA documentation defines, so it never launches.
+static bool gemm_operands_aligned(int in_dtype, const void* A, int64_t lda, const void* W, int64_t ldw) {
+  const int64_t ein = 16 / (int64_t)vcap_dt_size(in_dtype);
+  return (((uintptr_t)A | (uintptr_t)W) & 15) == 0 && lda % ein == 0 && ldw % ein == 0;
+}
+
 int vcap_gemm(int in_dtype, int out_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
               int64_t ldc, int M, int N, int K, const float* bias, int act, const float* res, int64_t ldr,
               int res_mode, int G, int Gs, int goff, int roff, void* stream) {
   if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return fail(VCAP_E_ARG, "vcap_gemm: bad arguments");
+  if (in_dtype != VCAP_DT_F32 && in_dtype != VCAP_DT_BF16 && in_dtype != VCAP_DT_F16)
+    return fail(VCAP_E_ARG, "vcap_gemm: operands must be VCAP_DT_F32, VCAP_DT_BF16 or VCAP_DT_F16");
   if (K % vcap_gemm_k_align(in_dtype)) return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: K must be a multiple of the K step");
+  if (!gemm_operands_aligned(in_dtype, A, lda, W, ldw))
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors");
   if (res_mode && !res) return fail(VCAP_E_ARG, "vcap_gemm: residual pointer missing");
   if ((res_mode == 2 || G) && G <= 0) return fail(VCAP_E_ARG, "vcap_gemm: row group G must be > 0");
   if (res_mode && out_dtype != VCAP_DT_F32) return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: residual needs f32 output");
   if (in_dtype == VCAP_DT_F16 && out_dtype != VCAP_DT_F16 && out_dtype != VCAP_DT_F32)
     return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: f16 operands write f16 or f32");
+  if (in_dtype == VCAP_DT_BF16 && out_dtype != VCAP_DT_BF16 && out_dtype != VCAP_DT_F32)
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: bf16 operands write bf16 or f32");
+  if (in_dtype == VCAP_DT_F32 && out_dtype != VCAP_DT_F32)
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm: f32 operands write f32");
   GemmEpi e{bias, res, (long)ldr, act, res_mode, G, Gs, goff, roff};
   vcap_err.clear();
   VCAP_TRY(vcap_gemm_dispatch(in_dtype, out_dtype, A, lda, W, ldw, C, ldc, M, N, K, e, (hipStream_t)stream),
@@ -140,6 +156,8 @@ int vcap_gemm_splitk(int in_dtype, const void* A, int64_t lda, const void* W, in
   if (in_dtype != VCAP_DT_BF16 && in_dtype != VCAP_DT_F16)
     return fail(VCAP_E_ARG, "vcap_gemm_splitk: operands must be VCAP_DT_BF16 or VCAP_DT_F16");
   if (K % vcap_gemm_k_align(in_dtype)) return fail(VCAP_E_UNSUPPORTED, "vcap_gemm_splitk: K must be a multiple of 64");
+  if (!gemm_operands_aligned(in_dtype, A, lda, W, ldw))
+    return fail(VCAP_E_UNSUPPORTED, "vcap_gemm_splitk: A, W 16-byte aligned; lda, ldw in whole 16-byte vectors");
   if (N % 4 || ldc % 4 || ((uintptr_t)C & 15) || ((uintptr_t)workspace & 15))
     return fail(VCAP_E_UNSUPPORTED, "vcap_gemm_splitk: N, ldc in whole 16-byte vectors; C and workspace 16-byte aligned");
   if (ws_bytes < (size_t)8 * M * N * sizeof(float)) return fail(VCAP_E_WORKSPACE, "vcap_gemm_splitk: workspace < 8*M*N*4 bytes");
