@@ -228,7 +228,12 @@ int vcap_frames_preprocess(const uint8_t* frames, int n, int in_h, int in_w, int
  *      3 components in one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0, restart markers.  The host
  *      parses and entropy-decodes (parallel threads, one image each); the device dequantises and runs
  *      jpeg_idct_islow, fancy-upsamples chroma and converts YCbCr -> RGB with libjpeg's fixed-point
- *      arithmetic, bit-identical to Pillow.  Progressive / arithmetic-coded / 12-bit / CMYK images ->
+ *      arithmetic: bit-identical to libjpeg's C decoder (jidctint.c, jdsample.c, jdcolor.c) for every
+ *      accepted stream, and to Pillow's default decode (libjpeg-turbo's SIMD IDCT) while no IDCT output
+ *      leaves [-512, 511] before the level shift - four times what real pixels give; beyond it the C code
+ *      wraps through its range table and the SIMD code saturates (DESIGN.md "JPEG decode sweep").  16-bit
+ *      DQT entries multiply as signed 16-bit values, as libjpeg-turbo holds them.  A chroma plane whose
+ *      downsampled width is 2 or less is refused.  Progressive / arithmetic-coded / 12-bit / CMYK images ->
  *      VCAP_E_UNSUPPORTED, and so are RGB-coded JPEGs (libjpeg's colour-space rule: no JFIF marker and
  *      an Adobe transform of 0, or component ids 'R','G','B').  vcap_jpeg_decode_batch: n images (HOST
  *      byte buffers) that share size and chroma sampling (each image keeps its own quantisation and

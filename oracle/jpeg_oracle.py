@@ -15,7 +15,9 @@ Huffman JPEGs (SOF0 / SOF1, 8-bit, 1 or 3 components, sampling factors 1 or 2, r
     filter with its 8 / 7 rounding biases, first / last column special cases, the top and bottom
     image rows replicated as context as jdmainct.c does);
   * jdcolor.c `ycc_rgb_convert` with its 16-bit fixed-point tables.
-Pinned bit-exact against Pillow's own decode of generated JPEGs (tests/test_cpu_jpeg.py).
+Pinned bit-exact against Pillow's own decode of generated JPEGs (tests/test_cpu_jpeg.py) and, over the case
+table of tests/jpeg_cases.py, against Pillow on libjpeg-turbo's C path (tests/test_cpu_jpeg_cases.py): beyond
+the coefficient range of real encodes this is jidctint.c's arithmetic, not the SIMD IDCT's.
 """
 from __future__ import annotations
 
@@ -54,7 +56,10 @@ def parse(data: bytes) -> dict:
                 n = 128 if pq else 64
                 vals = (np.frombuffer(seg[p + 1:p + 1 + n], ">u2") if pq else np.frombuffer(seg[p + 1:p + 65], "u1"))
                 q = np.zeros(64, np.int64)
-                q[ZIGZAG] = vals.astype(np.int64)       # natural order
+                # natural order; libjpeg-turbo keeps the IDCT's multipliers as 16-bit signed (ISLOW_MULT_TYPE is
+                # short in its SIMD builds, the ones Pillow ships): a 16-bit DQT entry >= 32768 multiplies as
+                # entry - 65536
+                q[ZIGZAG] = vals.astype(np.uint16).view(np.int16).astype(np.int64)
                 qt[tq] = q
                 p += 1 + n
         elif m in (0xC0, 0xC1):                         # SOF0 / SOF1

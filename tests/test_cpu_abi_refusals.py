@@ -15,11 +15,14 @@ used to come back from the dispatcher as -hipErrorInvalidValue ("invalid argumen
 entry point now asks vcap_vit_attention_supported before the dispatcher.  The rows of vcap_gemm / vcap_gemm_splitk came
 with the dense GEMM sweep (tests/test_gpu_gemm_sweep.py); "isnew" there: an operand dtype or an (operand, output) pair
 the dispatcher used to turn down as -hipErrorInvalidValue, and operands that are not 16-byte aligned with row strides in whole 16-byte vectors,
-which used to launch the 128x128 kernel's 16-byte LDS-DMA on misaligned addresses."""
+which used to launch the 128x128 kernel's 16-byte LDS-DMA on misaligned addresses.  The rows of vcap_frames_preprocess,
+vcap_jpeg_decode_batch and vcap_jpeg_probe came with the JPEG / preprocess sweep (tests/test_gpu_jpeg_sweep.py,
+tests/test_gpu_preprocess.py); "isnew" there: a null workspace, which vcap_frames_preprocess used to hand to its kernels."""
 import ctypes as C
 
 import pytest
 
+import jpeg_cases as JC
 from vcap import _native as N
 
 ARG, WS, UNSUP = N.E_ARG, N.E_WORKSPACE, N.E_UNSUPPORTED
@@ -65,6 +68,19 @@ def _samp(**kw):
 
 
 BIG = 1 << 30
+_MEAN, _STD = (C.c_float * 3)(0.485, 0.456, 0.406), (C.c_float * 3)(0.229, 0.224, 0.225)
+_JPEG = JC.case("samp_grey_8x8").data                                  # an accepted 8x8 image
+_SHORT_SOS = next(d[1] for d in JC.DAMAGED if d[0] == "sos_without_selectors")
+_BLOBS = {k: C.create_string_buffer(v, len(v)) for k, v in (("ok", _JPEG), ("short", _SHORT_SOS))}
+
+
+def _ptrs(key):
+    return (C.c_void_p * 1)(C.cast(_BLOBS[key], C.c_void_p))
+
+
+_LENS, _NOLEN = (C.c_size_t * 1)(len(_JPEG)), (C.c_size_t * 1)(0)
+_SHORT, _SHORT_LENS, _NULL_IMAGE = _ptrs("short"), (C.c_size_t * 1)(len(_SHORT_SOS)), (C.c_void_p * 1)(None)
+_NAMED = {id(_NOLEN): "zero", id(_SHORT): "short_sos", id(_SHORT_LENS): "short_sos", id(_NULL_IMAGE): "null_image"}
 # entry point -> its parameters in ABI order, each with a value every check accepts
 GOOD = {
     "generate": dict(d=_gpt2, gp=_gen, prefix=P, ids=[1], n=1, B=2, out=P, logits=None, ws=P, ws_bytes=BIG, stream=None),
@@ -89,10 +105,15 @@ GOOD = {
                  act=0, res=None, ldr=0, res_mode=0, G=0, Gs=0, goff=0, roff=0, stream=None),
     "gemm_splitk": dict(in_dt=N.DT_BF16, A=P, lda=384, W=P, ldw=384, C=P, ldc=16, M=4, N=16, K=384, bias=P, G=0, Gs=0,
                         ws=P, ws_bytes=BIG, splits=None, stream=None),
+    "frames_preprocess": dict(frames=P, n=2, in_h=16, in_w=16, out_h=8, out_w=8, mean=_MEAN, std=_STD, out=P, out_u8=None,
+                              ws=P, ws_bytes=BIG, stream=None),
+    "jpeg_decode_batch": dict(data=_ptrs("ok"), lens=_LENS, n=1, out=P, ws=P, ws_bytes=BIG, stream=None),
+    "jpeg_probe": dict(data=_JPEG, len=len(_JPEG), w=None, h=None, c=None),
 }
 SYMBOL = {"decode_attention": "vcap_decode_attention", "vit_encode": "vcap_vit_encode",
           "vit_layer_fuses": "vcap_vit_layer_fuses_qkv_attention", "vit_attention_mx": "vcap_vit_attention_mx",
-          "gemm": "vcap_gemm", "gemm_splitk": "vcap_gemm_splitk"}
+          "gemm": "vcap_gemm", "gemm_splitk": "vcap_gemm_splitk", "frames_preprocess": "vcap_frames_preprocess",
+          "jpeg_decode_batch": "vcap_jpeg_decode_batch", "jpeg_probe": "vcap_jpeg_probe"}
 
 # (entry point, the argument made bad, code, message, new?)   desc=/gp=/bp=/sp= give descriptor fields
 ROWS = [
@@ -217,6 +238,31 @@ ROWS = [
     ("gemm_splitk", dict(C=P + 4), UNSUP,
      "vcap_gemm_splitk: N, ldc in whole 16-byte vectors; C and workspace 16-byte aligned"),
     ("gemm_splitk", dict(ws_bytes=8 * 4 * 16 * 4 - 4), WS, "vcap_gemm_splitk: workspace < 8*M*N*4 bytes"),
+    ("frames_preprocess", dict(frames=None), ARG, "vcap_frames_preprocess: bad arguments"),
+    ("frames_preprocess", dict(mean=None), ARG, "vcap_frames_preprocess: bad arguments"),
+    ("frames_preprocess", dict(std=None), ARG, "vcap_frames_preprocess: bad arguments"),
+    ("frames_preprocess", dict(out=None), ARG, "vcap_frames_preprocess: bad arguments"),       # neither output
+    ("frames_preprocess", dict(ws=None), ARG, "vcap_frames_preprocess: bad arguments", "isnew"),
+    ("frames_preprocess", dict(n=0), ARG, "vcap_frames_preprocess: bad arguments"),
+    ("frames_preprocess", dict(n=-1), ARG, "vcap_frames_preprocess: bad arguments"),
+    ("frames_preprocess", dict(out_w=0), ARG, "vcap_frames_preprocess: bad arguments"),
+    # the downscale cap: 31 * 8 = 248 is served (tests/test_gpu_preprocess.py), 249 is not, on either axis
+    ("frames_preprocess", dict(in_w=249), UNSUP, "vcap_frames_preprocess: downscale factor above 31"),
+    ("frames_preprocess", dict(in_h=249), UNSUP, "vcap_frames_preprocess: downscale factor above 31"),
+    ("frames_preprocess", dict(in_w=32, out_w=1), UNSUP, "vcap_frames_preprocess: downscale factor above 31"),
+    ("frames_preprocess", dict(ws_bytes=255), WS, "vcap_frames_preprocess: workspace too small"),
+    ("jpeg_decode_batch", dict(data=None), ARG, "vcap_jpeg_decode_batch: bad arguments"),
+    ("jpeg_decode_batch", dict(lens=None), ARG, "vcap_jpeg_decode_batch: bad arguments"),
+    ("jpeg_decode_batch", dict(n=0), ARG, "vcap_jpeg_decode_batch: bad arguments"),
+    ("jpeg_decode_batch", dict(out=None), ARG, "vcap_jpeg_decode_batch: bad arguments"),
+    ("jpeg_decode_batch", dict(ws=None), ARG, "vcap_jpeg_decode_batch: bad arguments"),
+    ("jpeg_decode_batch", dict(lens=_NOLEN), ARG, "vcap_jpeg_decode_batch: empty image buffer"),
+    ("jpeg_decode_batch", dict(data=_NULL_IMAGE), ARG, "vcap_jpeg_decode_batch: empty image buffer"),
+    ("jpeg_decode_batch", dict(ws_bytes=255), WS, "vcap_jpeg_decode_batch: workspace too small"),
+    ("jpeg_decode_batch", dict(data=_SHORT, lens=_SHORT_LENS), ARG,
+     "vcap_jpeg_decode_batch: image 0: corrupt JPEG: SOS length", "isnew"),
+    ("jpeg_probe", dict(data=None), ARG, "vcap_jpeg_probe: bad arguments"),
+    ("jpeg_probe", dict(len=0), ARG, "vcap_jpeg_probe: bad arguments"),
 ]
 
 
@@ -240,9 +286,17 @@ def _call(entry, bad):
     return int(fn(*out)), N.lib().vcap_last_error().decode()
 
 
+def _ptr(v):
+    """An address inside _BUF as "ptr" / "ptr+offset": a test id must not carry a process address."""
+    if isinstance(v, int) and not isinstance(v, bool) and P < v < P + 4096:
+        return f"ptr+{v - P}"
+    return _NAMED.get(id(v), v)
+
+
 def _id(row):
     entry, bad = row[0], row[1]
-    parts = [f"{k}={'+'.join(f'{a}={b}' for a, b in v.items()) if isinstance(v, dict) else v}" for k, v in bad.items()]
+    parts = [f"{k}={'+'.join(f'{a}={b}' for a, b in v.items()) if isinstance(v, dict) else _ptr(v)}"
+             for k, v in bad.items()]
     return "-".join([entry] + parts + list(row[4:])).replace(str(P), "ptr")
 
 
@@ -284,3 +338,14 @@ def test_vit_workspace_query_is_zero_exactly_where_the_encode_refuses(dtype, fie
     desc = _vit(dtype=dtype, **fields)
     assert (int(N.lib().vcap_vit_workspace_bytes(C.byref(desc), 2, 3)) > 0) == served
     assert (int(N.lib().vcap_vit_layer_fuses_qkv_attention(C.byref(desc), 0)) >= 0) == served
+
+
+def test_frames_and_jpeg_workspace_queries_are_zero_for_bad_arguments():
+    lib = N.lib()
+    assert lib.vcap_frames_workspace_bytes(2, 16, 16, 8, 8) > 0
+    for bad in [(0, 16, 16, 8, 8), (-1, 16, 16, 8, 8), (2, 0, 16, 8, 8), (2, 16, 16, 8, 0)]:
+        assert lib.vcap_frames_workspace_bytes(*bad) == 0
+    assert lib.vcap_jpeg_workspace_bytes(_JPEG, len(_JPEG), 2) > lib.vcap_jpeg_workspace_bytes(_JPEG, len(_JPEG), 1) > 0
+    for bad in [(None, len(_JPEG), 1), (_JPEG, 0, 1), (_JPEG, len(_JPEG), 0), (_JPEG, len(_JPEG), -3),
+                (_SHORT_SOS, len(_SHORT_SOS), 1)]:
+        assert lib.vcap_jpeg_workspace_bytes(*bad) == 0

@@ -10,7 +10,12 @@
 //           vcap_frames_preprocess resizes and normalises.
 // Supported: 8-bit, 1 or 3 components in one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0, restart
 // markers.  Progressive / arithmetic / 12-bit / CMYK images are refused (VCAP_E_UNSUPPORTED).
-// Parity: tests/test_gpu_jpeg.py (bit-exact against Pillow and against oracle/jpeg_oracle.py).
+// Contract: bit-identical to libjpeg's C decoder for every accepted stream; bit-identical to Pillow's
+// default (SIMD) decode while no IDCT output leaves [-512, 511] before the level shift, which covers
+// every coefficient set a real encoder produces (beyond it C wraps through range_limit[x & 1023], the
+// SIMD IDCT saturates).  Parity: tests/test_gpu_jpeg.py (Pillow-written files) and
+// tests/test_gpu_jpeg_sweep.py (the case table of tests/jpeg_cases.py, built from chosen coefficients),
+// both against oracle/jpeg_oracle.py; the host stage under ASan / UBSan: tools/jpeg_host_check.sh.
 #include "../../include/vcap.h"
 #include "vcap_common.h"
 #include "vcap_kernels.h"
@@ -171,14 +176,25 @@ int parse(const uint8_t* d, size_t len, Parsed& p, std::string& err) {
                                  : (p.info.id[0] == 'R' && p.info.id[1] == 'G' && p.info.id[2] == 'B');
         if (rgb) return bad("RGB-coded JPEG (no YCbCr transform)");
       }
+      if (sl < 1) {
+        err = "corrupt JPEG: SOS length";
+        return VCAP_E_ARG;
+      }
       const int ns = s[0];
       if (ns != p.info.ncomp) return bad("only single-scan interleaved JPEGs");
+      if (sl < 1 + 2 * (size_t)ns) {  // the selectors below must lie inside the segment
+        err = "corrupt JPEG: SOS length";
+        return VCAP_E_ARG;
+      }
+      bool seen[3] = {false, false, false};
       for (int k = 0; k < ns; ++k) {
         const int cid = s[1 + 2 * k], t = s[2 + 2 * k];
         int c = -1;
         for (int j = 0; j < p.info.ncomp; ++j)
           if (p.info.id[j] == cid) c = j;
-        if (c < 0) return bad("SOS component id");
+        // every frame component once: one named twice would leave another's td / ta unset
+        if (c < 0 || seen[c]) return bad("SOS component id");
+        seen[c] = true;
         p.td[c] = t >> 4;
         p.ta[c] = t & 15;
         if (p.td[c] > 3 || p.ta[c] > 3 || !p.dc[p.td[c]].present || !p.ac[p.ta[c]].present) return bad("SOS tables");
@@ -371,6 +387,8 @@ __device__ __forceinline__ uint32_t vcap_jpeg_range(long v) {
 
 // qt: this component's table of image 0; image i's is qt + i * qt_stride (frames of one clip may
 // carry different tables: ffmpeg's MJPEG rate control writes a per-frame qscale into each DQT).
+// An entry multiplies as a signed 16-bit value, as libjpeg-turbo's ISLOW_MULT_TYPE table holds it
+// (short in the SIMD builds Pillow ships): a 16-bit DQT entry >= 32768 acts as entry - 65536.
 __global__ __launch_bounds__(256) void vcap_jpeg_idct_kernel(const int16_t* __restrict__ coef,
                                                              const uint16_t* __restrict__ qt, int qt_stride,
                                                              uint8_t* __restrict__ plane, int bx, int by,
@@ -387,7 +405,7 @@ __global__ __launch_bounds__(256) void vcap_jpeg_idct_kernel(const int16_t* __re
   // pass 1: column c, dequantised (the all-AC-zero shortcut is the same arithmetic)
   long d[8], r[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) d[k] = (long)in[k * 8 + c] * qt[k * 8 + c];
+  for (int k = 0; k < 8; ++k) d[k] = (long)in[k * 8 + c] * (int16_t)qt[k * 8 + c];
   vcap_idct_1d(d, r);
 #pragma unroll
   for (int k = 0; k < 8; ++k) ws[lb][k][c] = (int)((r[k] + (1L << (CB - P1 - 1))) >> (CB - P1));
@@ -493,8 +511,12 @@ size_t vcap_jpeg_ws_bytes(const JpegInfo& f, int n) {
   return ((ce * sizeof(int16_t) + 255) & ~(size_t)255) + pb + (size_t)n * 3 * 64 * sizeof(uint16_t) + 256;
 }
 
-int vcap_jpeg_decode(const uint8_t* const* data, const size_t* lens, int n, uint8_t* out, void* ws, size_t ws_bytes,
-                     hipStream_t s, std::string* err) {
+// The host stage of vcap_jpeg_decode, with no device call of its own: parse the n images (one size
+// and sampling), then entropy-decode them on host threads into the buffer `stage` hands out: the
+// coefficients (component-major, jpeg_layout's order), then from the next 16-byte boundary every
+// image's own quantisation tables, [image][component][64] natural order.
+int vcap_jpeg_host_stage(const uint8_t* const* data, const size_t* lens, int n, JpegInfo* info,
+                         const JpegStageAlloc& stage, std::string* err) {
   std::vector<Parsed> ps(n);
   std::string e;
   for (int i = 0; i < n; ++i) {
@@ -516,46 +538,80 @@ int vcap_jpeg_decode(const uint8_t* const* data, const size_t* lens, int n, uint
     *err = "batch larger than 2 GiB of RGB";
     return VCAP_E_UNSUPPORTED;
   }
-  if (ws_bytes < vcap_jpeg_ws_bytes(f, n)) {
-    *err = "workspace too small";
-    return VCAP_E_WORKSPACE;
-  }
+  *info = f;
   size_t comp_off[3], coef_elems, plane_off[3], plane_bytes;
   jpeg_layout(f, n, comp_off, &coef_elems, plane_off, &plane_bytes);
-  // entropy decode: the serial stage, one host thread per group of images, into a pinned staging
-  // buffer (kept for the process: pageable memory halved the upload rate of the coefficients,
-  // which are n x 128 B per 8x8 block)
-  std::lock_guard<std::mutex> lock(g_stage_mu);
-  const size_t stage_need = ((coef_elems * sizeof(int16_t) + 15) & ~(size_t)15) + (size_t)n * 3 * 64 * sizeof(uint16_t);
-  if (g_stage_bytes < stage_need) {
-    if (g_stage) (void)hipHostFree(g_stage);
-    g_stage = nullptr;
-    g_stage_bytes = 0;
-    const size_t want = stage_need + stage_need / 4;
-    if (hipHostMalloc(&g_stage, want, hipHostMallocDefault) != hipSuccess) {
-      g_stage = nullptr;
-      *err = "jpeg decode: pinned staging allocation failed";
-      return -(int)hipErrorOutOfMemory;
-    }
-    g_stage_bytes = want;
-  }
-  int16_t* coef = (int16_t*)g_stage;
+  int rc = 0;
+  void* buf = stage(f, vcap_jpeg_stage_bytes(f, n), &rc, err);
+  if (!buf) return rc;
+  // entropy decode: the serial stage, one host thread per group of images
+  int16_t* coef = (int16_t*)buf;
   const int nt = std::max(1, std::min<int>({n, (int)std::thread::hardware_concurrency(), 16}));
-  std::atomic<int> next{0};
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&] {
-      for (int i = next++; i < n; i = next++) decode_coefficients(ps[i], i, n, coef, comp_off);
-    });
-  for (auto& t : th) t.join();
+  if (nt == 1) {
+    for (int i = 0; i < n; ++i) decode_coefficients(ps[i], i, n, coef, comp_off);
+  } else {
+    std::atomic<int> next{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+      th.emplace_back([&] {
+        for (int i = next++; i < n; i = next++) decode_coefficients(ps[i], i, n, coef, comp_off);
+      });
+    for (auto& t : th) t.join();
+  }
+  uint16_t* qts = (uint16_t*)((char*)buf + ((coef_elems * sizeof(int16_t) + 15) & ~(size_t)15));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < f.ncomp; ++k) std::memcpy(qts + ((size_t)i * f.ncomp + k) * 64, ps[i].qt[ps[i].tq[k]], 128);
+  return 0;
+}
+
+size_t vcap_jpeg_stage_bytes(const JpegInfo& f, int n) {
+  size_t co[3], ce, po[3], pb;
+  jpeg_layout(f, n, co, &ce, po, &pb);
+  return ((ce * sizeof(int16_t) + 15) & ~(size_t)15) + (size_t)n * 3 * 64 * sizeof(uint16_t);
+}
+
+int vcap_jpeg_decode(const uint8_t* const* data, const size_t* lens, int n, uint8_t* out, void* ws, size_t ws_bytes,
+                     hipStream_t s, std::string* err) {
+  // the pinned staging buffer (kept for the process: pageable memory halved the upload rate of the
+  // coefficients, which are n x 128 B per 8x8 block) is taken, under its lock, once the headers
+  // have been parsed and the workspace is known to hold the batch
+  std::unique_lock<std::mutex> lock(g_stage_mu, std::defer_lock);
+  JpegInfo f;
+  const int rc = vcap_jpeg_host_stage(
+      data, lens, n, &f,
+      [&](const JpegInfo& fi, size_t stage_need, int* arc, std::string* aerr) -> void* {
+        if (ws_bytes < vcap_jpeg_ws_bytes(fi, n)) {
+          *aerr = "workspace too small";
+          *arc = VCAP_E_WORKSPACE;
+          return nullptr;
+        }
+        lock.lock();
+        if (g_stage_bytes < stage_need) {
+          if (g_stage) (void)hipHostFree(g_stage);
+          g_stage = nullptr;
+          g_stage_bytes = 0;
+          const size_t want = stage_need + stage_need / 4;
+          if (hipHostMalloc(&g_stage, want, hipHostMallocDefault) != hipSuccess) {
+            g_stage = nullptr;
+            *aerr = "jpeg decode: pinned staging allocation failed";
+            *arc = -(int)hipErrorOutOfMemory;
+            return nullptr;
+          }
+          g_stage_bytes = want;
+        }
+        return g_stage;
+      },
+      err);
+  if (rc) return rc;
+  size_t comp_off[3], coef_elems, plane_off[3], plane_bytes;
+  jpeg_layout(f, n, comp_off, &coef_elems, plane_off, &plane_bytes);
+  const int16_t* coef = (const int16_t*)g_stage;
   char* w = (char*)ws;
   int16_t* d_coef = (int16_t*)w;
   uint8_t* d_planes = (uint8_t*)(w + ((coef_elems * sizeof(int16_t) + 255) & ~(size_t)255));
   uint16_t* d_qt = (uint16_t*)(d_planes + plane_bytes);
   // every image's own tables, [image][component][64] natural order, staged behind the coefficients
-  uint16_t* qts = (uint16_t*)((char*)g_stage + ((coef_elems * sizeof(int16_t) + 15) & ~(size_t)15));
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < f.ncomp; ++k) std::memcpy(qts + ((size_t)i * f.ncomp + k) * 64, ps[i].qt[ps[i].tq[k]], 128);
+  const uint16_t* qts = (const uint16_t*)((char*)g_stage + ((coef_elems * sizeof(int16_t) + 15) & ~(size_t)15));
   hipError_t he = hipMemcpyAsync(d_coef, coef, coef_elems * sizeof(int16_t), hipMemcpyHostToDevice, s);
   // from here on the pinned staging buffer may be read by an in-flight copy: every return below
   // synchronises the stream first (the next call reuses or frees the buffer)

@@ -243,7 +243,8 @@ size_t vcap_frames_workspace_bytes(int n, int in_h, int in_w, int out_h, int out
 int vcap_frames_preprocess(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const float* mean3,
                            const float* std3, float* out, uint8_t* out_u8, void* workspace, size_t ws_bytes,
                            void* stream) {
-  if (!frames || n <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || !mean3 || !std3 || (!out && !out_u8))
+  if (!frames || n <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || !mean3 || !std3 || (!out && !out_u8) ||
+      !workspace)
     return fail(VCAP_E_ARG, "vcap_frames_preprocess: bad arguments");
   if (in_w > 31 * out_w || in_h > 31 * out_h)
     return fail(VCAP_E_UNSUPPORTED, "vcap_frames_preprocess: downscale factor above 31");

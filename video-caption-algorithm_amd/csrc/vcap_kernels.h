@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 
 struct GemmEpi {
@@ -401,3 +402,12 @@ int vcap_jpeg_header(const uint8_t* data, size_t len, JpegInfo* info, std::strin
 size_t vcap_jpeg_ws_bytes(const JpegInfo& f, int n);
 int vcap_jpeg_decode(const uint8_t* const* data, const size_t* lens, int n, uint8_t* out, void* ws, size_t ws_bytes,
                      hipStream_t s, std::string* err);
+// The host stage of vcap_jpeg_decode alone (no device call; tools/jpeg_host_check.cpp runs it under the
+// host sanitizers): parse n images of one shape into *info, then entropy-decode them into the buffer
+// `stage` returns for (shape, bytes = vcap_jpeg_stage_bytes): the int16 coefficients, then from the next
+// 16-byte boundary the images' quantisation tables [image][component][64].  A null buffer ends the call
+// with the *rc / *err the allocator set.
+using JpegStageAlloc = std::function<void*(const JpegInfo& f, size_t bytes, int* rc, std::string* err)>;
+size_t vcap_jpeg_stage_bytes(const JpegInfo& f, int n);
+int vcap_jpeg_host_stage(const uint8_t* const* data, const size_t* lens, int n, JpegInfo* info,
+                         const JpegStageAlloc& stage, std::string* err);

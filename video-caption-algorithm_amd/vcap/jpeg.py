@@ -2,9 +2,13 @@
 
 Replaces the host `Image.open(path).convert("RGB")` of core/preprocessing/frame_loader.py:42-44 for
 baseline JPEGs: the library parses and entropy-decodes on host threads and runs libjpeg-turbo's
-islow IDCT, fancy chroma upsampling and YCbCr -> RGB on the device, bit-identical to Pillow
-(tests/test_gpu_jpeg.py).  Images the decoder does not take (progressive, arithmetic-coded, CMYK,
-4:4:0 ...) raise VcapError; there is no host fallback.
+islow IDCT, fancy chroma upsampling and YCbCr -> RGB on the device.  The output is bit-identical to
+libjpeg's C decoder for every accepted stream, and to Pillow's default (SIMD) decode while the
+coefficients stay in the range a real encoder produces: no IDCT output outside [-512, 511] before the
+level shift; past that the C code wraps and the SIMD code saturates (tests/test_gpu_jpeg.py,
+tests/test_gpu_jpeg_sweep.py, DESIGN.md "JPEG decode sweep").  Images the decoder does not take
+(progressive, arithmetic-coded, CMYK, 4:4:0, a downsampled chroma width of 2 or less ...) raise
+VcapError; there is no host fallback.
 """
 from __future__ import annotations
 
