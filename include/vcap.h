@@ -37,6 +37,10 @@
  *                           faiss.IndexIVFFlat train / add / search with METRIC_INNER_PRODUCT
  *                           (build_faiss of scripts/build_index_with_captions.py:33-45)
  *   vcap_text_encode        ViTTextAlignModel.encode_text (src/models/vit_text_align.py:67-79)
+ *   vcap_vit_encode_backward / vcap_vit_attention_backward
+ *                           loss.backward() through ViTTextAlignModel.encode_video's ViT with freeze_vit
+ *                           off (src/cli/train_full.py:47, :124-130: AdamW over model.parameters()); the
+ *                           optimiser itself stays in torch
  */
 #ifndef VCAP_H_
 #define VCAP_H_
@@ -809,6 +813,93 @@ size_t vcap_gpt2_beam_search_ragged_workspace_bytes(const vcap_gpt2_desc* d, con
 int vcap_gpt2_beam_search_ragged(const vcap_gpt2_desc* d, const vcap_beam_params* bp, const float* prefix,
                                  const vcap_prompts* prompts, int B, int* out_ids, int* out_len, void* workspace,
                                  size_t ws_bytes, void* stream);
+
+/* ---- ViT training (added within ABI v16: new symbols and structs only): the gradient of any scalar of
+ *      vcap_vit_encode's enc_out with respect to the encoder's trainable parameters - autograd of
+ *      ViTFrameEncoder.forward as src/cli/train_full.py --model vit trains it (timm's ViT has no dropout).
+ *      One call runs vcap_vit_encode's schedule and walks back through the last n_tail blocks (1 .. depth).
+ *      It returns, as device f32 tensors in timm's own layouts, the gradients of encoder.proj (weight, bias),
+ *      the final norm (gamma, beta) and the 12 tensors of each of the last n_tail blocks; with n_tail == depth
+ *      also patch_embed.proj.weight (as [dim, kpad]: the flattened [dim, 3*p*p] kernel, pad columns +0),
+ *      patch_embed.proj.bias, cls_token [dim] and pos_embed [tokens, dim]; those four pointers may be NULL
+ *      otherwise.  grads->layers[j] is block depth - n_tail + j.  Blocks below the tail run exactly as
+ *      vcap_vit_encode runs them and keep nothing; the walk stops at the first unfrozen block's input.
+ *      enc_out has vcap_vit_encode's bits: in the unfrozen blocks the QKV projection + attention run as the
+ *      GEMM + attention pair (bit-identical to the fused kernel), the last block stays the CLS-only tail.
+ *      Per unfrozen block the forward keeps the f32 stream at the block input and after the attention
+ *      residual, q | k | v, the attention output and the GELU output (operand dtype); the LayerNorm outputs and
+ *      the fc1 pre-activation are recomputed, the latter in f32 (fc1 without its GELU epilogue), so gelu' is
+ *      never taken from a rounded pre-activation.
+ *      The grad desc holds operand-dtype, plain row-major TRANSPOSED ([in, out]) copies of the four Linear
+ *      weights of every block (blocks below the tail are not read and may be NULL) and, for the caller's
+ *      bookkeeping only, the f32 masters they were rounded from (never dereferenced by the library).
+ *      Operand dtypes: VCAP_DT_F32 and VCAP_DT_BF16; VCAP_DT_F16 and VCAP_DT_MXFP8 are VCAP_E_UNSUPPORTED
+ *      before any launch.  Widths: dim % 128 == 0 (head dim 64, dim <= 1024: ViT-S / B / L) and mlp % 128 == 0
+ *      are served, every other width is VCAP_E_UNSUPPORTED before any launch; token counts are the ones
+ *      vcap_vit_encode serves in these dtypes (1..32, 193..224, 257..288).
+ *      bf16: every MFMA operand is bf16 (RNE) - q | k | v, P, dS, dO and each Linear's dY once, when it enters a
+ *      product; accumulation, the residual gradient, softmax, LayerNorm / GELU backward and all bias / affine
+ *      sums are f32.  An f32 desc rounds nowhere.  No float atomics; every sum has one order that depends on
+ *      (B, T, n_tail, the architecture) only: 32-row tiles in order inside constant 256-row slabs added in slab
+ *      order (weights); rows w, w + 4, ... per wave w = 0..3, partials added in wave order (biases, gamma,
+ *      beta); frames in order (pos, cls); videos in order (encoder.proj).  A video whose grad_out row is +0
+ *      adds exactly +0 to every gradient; doubling grad_out doubles every gradient exactly.
+ *      Alignment: the workspace 256-byte aligned; the grad desc's transposed copies (qkv_t, proj_t, fc1_t, fc2_t
+ *      of the unfrozen blocks) and the weight gradients (qkv_w, proj_w, fc1_w, fc2_w of every returned block,
+ *      patch_w) 16-byte aligned; frames, grad_out and the other gradients need their element alignment only.
+ *      Size of one call: B * T * heads <= 65535 and B * T * tokens <= 2^22 (larger batches go in chunks, whose
+ *      gradients the caller adds).
+ *      Return codes, every one before the first launch and writing nothing (the workspace query returns 0
+ *      outside the limits): VCAP_E_ARG - null pointers (a NULL embedding gradient only with n_tail == depth),
+ *      B / T < 1, n_tail outside 1 .. depth, a grad desc whose dtype / dim / mlp / depth differ from the vit
+ *      desc's; VCAP_E_UNSUPPORTED - the descriptor limits of vcap_vit_encode, an operand dtype or width outside
+ *      the ones above, a call over the size limits, a workspace that is not 256-byte aligned, a transposed copy or
+ *      weight gradient that is not 16-byte aligned; VCAP_E_WORKSPACE - ws_bytes below
+ *      vcap_vit_backward_workspace_bytes.
+ *      One training step through an autograd wrapper that calls vcap_vit_encode in its forward and this call in
+ *      its backward (vcap.train_align.EncodeVideo) runs the encoder forward twice: once for enc_out, once more
+ *      inside this call, which keeps no state between calls.
+ *      vcap_vit_attention_backward is the attention backward alone, at every token count 1..288: qkv
+ *      [frames*tokens][3*64*heads] in `dtype`, dout f32 [frames*tokens][64*heads] -> dqkv f32 (dq | dk | dv).
+ *      Per (frame, head): S = Q K^T / 8 and the softmax by the forward kernels' expressions, dP = dO V^T,
+ *      delta = rowsum(P dP), dS = P (dP - delta) / 8, dQ = dS K, dK = dS^T Q, dV = P^T dO on the MFMA; keys
+ *      past the token count contribute exactly 0.  Null pointers and sizes < 1: VCAP_E_ARG; another dtype,
+ *      tokens > 288, frames * heads > 65535, qkv / dout / dqkv not 16-byte or the workspace not 256-byte aligned:
+ *      VCAP_E_UNSUPPORTED (the workspace query returns 0), all before any launch. ---- */
+typedef struct vcap_vit_grad_layer {
+  const void* qkv_t;   /* [D, 3D]  = attn.qkv.weight^T,  operand dtype */
+  const void* proj_t;  /* [D, D]   = attn.proj.weight^T */
+  const void* fc1_t;   /* [D, mlp] = mlp.fc1.weight^T   */
+  const void* fc2_t;   /* [mlp, D] = mlp.fc2.weight^T   */
+  const float* qkv_m; const float* proj_m; const float* fc1_m; const float* fc2_m;   /* f32 masters, [out, in] */
+} vcap_vit_grad_layer;
+typedef struct vcap_vit_grad_desc {
+  int dtype, dim, mlp, depth;              /* must equal the vit desc's */
+  const vcap_vit_grad_layer* layers;       /* host array of depth entries */
+} vcap_vit_grad_desc;
+typedef struct vcap_vit_param_grads_layer {   /* device f32 */
+  float* ln1_g; float* ln1_b;
+  float* qkv_w; float* qkv_b;     /* [3D, D], [3D] */
+  float* proj_w; float* proj_b;   /* [D, D], [D]   */
+  float* ln2_g; float* ln2_b;
+  float* fc1_w; float* fc1_b;     /* [mlp, D], [mlp] */
+  float* fc2_w; float* fc2_b;     /* [D, mlp], [D]   */
+} vcap_vit_param_grads_layer;
+typedef struct vcap_vit_param_grads {
+  float* proj_w; float* proj_b;   /* encoder.proj [video_dim, dim], [video_dim] */
+  float* norm_g; float* norm_b;   /* [dim] */
+  float* patch_w; float* patch_b; /* [dim, kpad], [dim]      (n_tail == depth) */
+  float* cls; float* pos;         /* [dim], [tokens, dim]    (n_tail == depth) */
+  const vcap_vit_param_grads_layer* layers;   /* host array of n_tail entries: blocks depth - n_tail .. depth - 1 */
+} vcap_vit_param_grads;
+size_t vcap_vit_backward_workspace_bytes(const vcap_vit_desc* d, int B, int T, int n_tail);
+int vcap_vit_encode_backward(const vcap_vit_desc* d, const vcap_vit_grad_desc* g, const float* frames, int B, int T,
+                             int n_tail, const float* grad_out /* device [B][video_dim] */,
+                             float* enc_out /* device [B][video_dim] */, const vcap_vit_param_grads* grads,
+                             void* workspace, size_t ws_bytes, void* stream);
+size_t vcap_vit_attention_backward_workspace_bytes(int dtype, int frames, int tokens, int heads);
+int vcap_vit_attention_backward(int dtype, const void* qkv, const float* dout, float* dqkv, int frames, int tokens,
+                                int heads, void* workspace /* 256-byte aligned */, void* stream);
 
 /* ---- live kernel timing for the benchmark's roofline (sites: "vit.qkv", "vit.attention",
  *      "vit.proj", "vit.fc1", "vit.fc2"): events are recorded around each launch of the site on

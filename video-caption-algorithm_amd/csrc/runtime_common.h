@@ -95,6 +95,24 @@ struct TextSnap {   // what the forward keeps for the backward, layer-major (M =
 int vcap_text_forward(const vcap_text_desc* d, const int* ids, int B, int L, float* out, float* hidden_out,
                       void* workspace, const TextSnap* snap, hipStream_t s);
 
+// ---- runtime_vit.hip, for the encoder's backward (runtime_vit_grad.hip)
+int vcap_vit_check(const vcap_vit_desc* d);   // the descriptor limits of every ViT entry point
+struct VitSnap {   // what the forward keeps of its last n_tail blocks, block-major (M = B*T*tokens rows, T = operand dtype)
+  int n_tail;
+  float* x0;       // [n_tail][M][D] f32 stream at the block input
+  float* x1;       // [n_tail][M][D] f32 stream after the attention residual (the last block: its B*T CLS rows, compact)
+  char* qkv;       // [n_tail][M][3D] T
+  char* attn;      // [n_tail][M][D] T (the last block: [B*T][D])
+  char* act;       // [n_tail][M][mlp] T (the last block: [B*T][mlp])
+  // set by the forward: pieces of its workspace - the final stream, the LayerNorm output buffer (free after the
+  // forward) and the im2col patches (intact when every block is kept)
+  float* x;
+  void* xn;
+  void* patches;
+};
+int vcap_vit_forward(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const float* frames, int B, int T,
+                     float* enc_out, float* prefix_out, void* workspace, VitSnap* snap, hipStream_t s);
+
 // ---- graph_cache.hip
 // Bytes of everything a captured decode bakes in; two calls replay one graph only if their keys are equal.
 struct GraphKey {

@@ -165,7 +165,20 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
   if (!frames || !enc_out || B <= 0 || T <= 0) return fail(VCAP_E_ARG, "vcap_vit_encode: bad arguments");
   if (prefix_out && (!pd || !pd->mapper_w)) return fail(VCAP_E_ARG, "vcap_vit_encode: prefix desc missing");
   if (ws_bytes < vcap_vit_workspace_bytes(d, B, T)) return fail(VCAP_E_WORKSPACE, "vcap_vit_encode: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
+  return vcap_vit_forward(d, pd, frames, B, T, enc_out, prefix_out, workspace, nullptr, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+int vcap_vit_check(const vcap_vit_desc* d) { return check_vit(d); }
+
+// vcap_vit_encode's schedule (arguments checked by the caller).  With `snap` (vcap_vit_encode_backward) the last
+// snap->n_tail blocks keep what their backward reads: the f32 stream at the block input and after the attention
+// residual is copied out, q | k | v, the attention output and the GELU output land in buffers of their own, and
+// the QKV projection + attention run as the GEMM + attention pair (the fused kernel's bits,
+// tests/test_gpu_qkv_attention.py) so that q | k | v reach HBM.  The blocks below run exactly as without it.
+int vcap_vit_forward(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const float* frames, int B, int T,
+                     float* enc_out, float* prefix_out, void* workspace, VitSnap* snap, hipStream_t s) {
   Carver c(workspace);
   VitBufs w = carve_vit(c, d, B, T);
   const int dt = d->dtype, D = d->dim, g = d->image / d->patch, P = g * g, N = P + 1, BT = B * T;
@@ -183,10 +196,11 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
     return 0;
   };
   // patch embedding: im2col + GEMM whose epilogue adds bias + pos[1+p] and scatters row bt*N+1+p
-  VCAP_TRY(vcap_patchify_dispatch(adt, frames, w.act, w.x, d->cls, d->pos, BT, d->image, d->patch, d->kpad, N, D, s),
+  void* const patches = w.act;
+  VCAP_TRY(vcap_patchify_dispatch(adt, frames, patches, w.x, d->cls, d->pos, BT, d->image, d->patch, d->kpad, N, D, s),
            "patchify");
   GemmEpi pe{d->patch_b, d->pos, D, 0, 2, P, N, 1, 1};
-  VCAP_TRY(vcap_gemm_dispatch(adt, VCAP_DT_F32, w.act, d->kpad, d->patch_w, d->kpad, w.x, D, BT * P, D, d->kpad, pe, s),
+  VCAP_TRY(vcap_gemm_dispatch(adt, VCAP_DT_F32, patches, d->kpad, d->patch_w, d->kpad, w.x, D, BT * P, D, d->kpad, pe, s),
            "patch_gemm");
   for (int l = 0; l < d->depth; ++l) {
     const vcap_vit_layer& ly = d->layers[l];
@@ -197,6 +211,14 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
     // remapped to x[bt*N] (GemmEpi G = 1, Gs = N).  Outputs are identical; 6 % fewer FLOPs.
     const bool last = l == d->depth - 1;
     const int Mt = last ? BT : M;                       // rows after the QKV projection
+    const int slot = snap ? l - (d->depth - snap->n_tail) : -1;   // >= 0: a block whose activations are kept
+    if (slot >= 0) {
+      const size_t ea = esize(adt), n = (size_t)M * D;
+      VCAP_TRY(hipMemcpyAsync(snap->x0 + slot * n, w.x, n * 4, hipMemcpyDeviceToDevice, s), "snapshot x0");
+      w.qkv = snap->qkv + slot * 3 * n * ea;
+      w.attn = snap->attn + slot * n * ea;
+      w.act = snap->act + (size_t)slot * M * d->mlp * ea;
+    }
     const std::string probe_attn = vit_site("attention", last);
     // MXFP8 mode, per GEMM (weight scales present): the producer of its A operand emits MXFP8
     const bool mq = mx && ly.qkv_ws, mp = mx && ly.proj_ws, m1 = mx && ly.fc1_ws, m2 = mx && ly.fc2_ws;
@@ -204,7 +226,7 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
     const int d1 = m1 ? VCAP_DT_MXFP8 : adt, d2 = m2 ? VCAP_DT_MXFP8 : adt;
     if (int rc = norm(mq, D, ly.ln1_g, ly.ln1_b, M, "norm1")) return rc;
     GemmEpi e1{ly.qkv_b, nullptr, 0, 0, 0, 0, 0, 0, 0, mq ? w.xn_s : nullptr, mq ? ly.qkv_ws : nullptr, nullptr};
-    if (vit_layer_fused(d, ly)) {
+    if (slot < 0 && vit_layer_fused(d, ly)) {
       // QKV projection + attention in one kernel: q / k / v stay on chip
       ProbeScope ps(probe_attn.c_str(), s, M);
       VCAP_TRY(vcap_vit_qkv_attention_dispatch(adt, w.xn, ly.qkv_w, ly.qkv_b, w.attn, BT, N, d->heads, last, s),
@@ -226,6 +248,13 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
     {
       ProbeScope ps(vit_site("proj", last).c_str(), s, Mt);
       VCAP_TRY(vcap_gemm_dispatch(dp, VCAP_DT_F32, w.attn, D, ly.proj_w, D, w.x, D, Mt, D, D, e2, s), "attn_proj");
+    }
+    if (slot >= 0) {   // the stream after the attention residual (the last block: its BT class-token rows)
+      float* x1 = snap->x1 + (size_t)slot * M * D;
+      if (last)
+        VCAP_TRY(vcap_vit_rows_copy_dispatch(w.x, (long)N * D, x1, D, BT, D, s), "snapshot x1");
+      else
+        VCAP_TRY(hipMemcpyAsync(x1, w.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s), "snapshot x1");
     }
     // CLS rows of x are N*D apart
     if (int rc = norm(m1, last ? (long)N * D : D, ly.ln2_g, ly.ln2_b, Mt, "norm2")) return rc;
@@ -260,7 +289,10 @@ int vcap_vit_encode(const vcap_vit_desc* d, const vcap_prefix_desc* pd, const fl
                                          pd ? pd->mapper_b : nullptr, MO, enc_out, prefix_out, nullptr,
                                          (float*)w.xn, s, dt == VCAP_DT_F16),
            "head_prefix");
+  if (snap) {
+    snap->x = w.x;
+    snap->xn = w.xn;
+    snap->patches = patches;
+  }
   return 0;
 }
-
-}  // extern "C"

@@ -391,6 +391,41 @@ hipError_t vcap_text_attn_bwd_dispatch(int dt, const void* qkv, const float* dO,
 hipError_t vcap_text_emb_grad_dispatch(const int* ids, int M, int pad_id, int vocab, const float* a, const float* b,
                                        int E, int* slot, int* emb_ids, int* count, float* rows, hipStream_t s);
 
+// ---- ViT backward (csrc/vit_backward.hip): parameter gradients of the encoder, f32 outputs, fixed orders ----
+// C [K, N] f32 = sum over rows of X[row][k] Y[row][n], X [rows, Kmem >= K] and Y [rows, N] row-major in dt (f32 or
+// bf16).  Launch batch z = (z1, z2) = (z / Z2, z % Z2) takes rows [0, min(slab_rows, rows_total - z1 * slab_step))
+// of X + z1 xs1 + z2 xs2 and Y + z1 ys1 + z2 ys2 into C + z1 cs1 + z2 cs2 (offsets in elements).
+struct XtyArgs {
+  const void* X;
+  long ldx;
+  int Kmem;
+  const void* Y;
+  long ldy;
+  int N;
+  float* C;
+  long ldc;
+  int K;
+  int rows_total, slab_rows, slab_step;
+  int Z2;
+  long xs1, xs2, ys1, ys2, cs1, cs2;
+};
+hipError_t vcap_vit_xty_dispatch(int dt, const XtyArgs& a, int Z, hipStream_t s);
+// row stride (and row count) of one (frame, head)'s P / dS / dS^T scratch matrix: N rounded up to 64
+int vcap_vit_attn_bwd_ldp(int N);
+// qkv (dt) [BT*N, 3 * 64 H], dO (dt) [BT*N, 64 H]; P, dS, dST: [BT*H][ldp][ldp] dt scratch; dqkv f32
+// [BT*N, 3 * 64 H].  1 <= N <= 288.
+hipError_t vcap_vit_attn_bwd_dispatch(int dt, const void* qkv, const void* dO, int BT, int N, int H, void* P, void* dS,
+                                      void* dST, float* dqkv, hipStream_t s);
+// xn [B*T, D]: the final norm of the CLS rows.  pooled [B, D], dn [B*T, D] = (gout . pw) / T, then dproj_w [VD, D]
+// and dproj_b [VD], videos in order
+hipError_t vcap_vit_head_bwd_dispatch(const float* xn, int B, int T, int D, const float* gout, const float* pw, int VD,
+                                      float* pooled, float* dn, float* dproj_w, float* dproj_b, hipStream_t s);
+// dpos [N, D] = sum over the BT frames in order of g [BT*N, D]; dcls [D] = dpos[0]
+hipError_t vcap_vit_pos_grad_dispatch(const float* g, int BT, int N, int D, float* dpos, float* dcls, hipStream_t s);
+// dst[r * ldd + i] = src[r * lds + i] for r < rows, i < width (f32)
+hipError_t vcap_vit_rows_copy_dispatch(const float* src, long lds, float* dst, long ldd, int rows, long width,
+                                       hipStream_t s);
+
 // JPEG frame decode (jpeg.hip): header of one baseline image, workspace of n same-shape images,
 // host entropy decode + device IDCT / upsampling / colour conversion into uint8 [n, H, W, 3].
 struct JpegInfo {

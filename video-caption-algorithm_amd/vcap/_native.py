@@ -129,6 +129,25 @@ class TextParamGrads(C.Structure):
                 ("layers", C.POINTER(TextParamGradsLayer))]
 
 
+class VitGradLayer(C.Structure):
+    _fields_ = [("qkv_t", vp), ("proj_t", vp), ("fc1_t", vp), ("fc2_t", vp),
+                ("qkv_m", vp), ("proj_m", vp), ("fc1_m", vp), ("fc2_m", vp)]
+
+
+class VitGradDesc(C.Structure):
+    _fields_ = [("dtype", i32), ("dim", i32), ("mlp", i32), ("depth", i32), ("layers", C.POINTER(VitGradLayer))]
+
+
+class VitParamGradsLayer(C.Structure):
+    _fields_ = [("ln1_g", vp), ("ln1_b", vp), ("qkv_w", vp), ("qkv_b", vp), ("proj_w", vp), ("proj_b", vp),
+                ("ln2_g", vp), ("ln2_b", vp), ("fc1_w", vp), ("fc1_b", vp), ("fc2_w", vp), ("fc2_b", vp)]
+
+
+class VitParamGrads(C.Structure):
+    _fields_ = [("proj_w", vp), ("proj_b", vp), ("norm_g", vp), ("norm_b", vp), ("patch_w", vp), ("patch_b", vp),
+                ("cls", vp), ("pos", vp), ("layers", C.POINTER(VitParamGradsLayer))]
+
+
 # name -> (restype, argtypes); every symbol include/vcap.h declares
 SIGNATURES = {
     "vcap_last_error": (C.c_char_p, []),
@@ -208,6 +227,11 @@ SIGNATURES = {
     "vcap_text_encode_backward_workspace_bytes": (sz, [C.POINTER(TextDesc), C.POINTER(TextGradDesc), i32, i32]),
     "vcap_text_encode_backward": (i32, [C.POINTER(TextDesc), C.POINTER(TextGradDesc), vp, i32, i32, vp,
                                         C.POINTER(TextParamGrads), vp, vp, sz, vp]),
+    "vcap_vit_backward_workspace_bytes": (sz, [C.POINTER(VitDesc), i32, i32, i32]),
+    "vcap_vit_encode_backward": (i32, [C.POINTER(VitDesc), C.POINTER(VitGradDesc), vp, i32, i32, i32, vp, vp,
+                                       C.POINTER(VitParamGrads), vp, sz, vp]),
+    "vcap_vit_attention_backward_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "vcap_vit_attention_backward": (i32, [i32, vp, vp, vp, i32, i32, i32, vp, vp]),
     "vcap_gpt2_ragged_workspace_bytes": (sz, [C.POINTER(GPT2Desc), C.POINTER(C.c_int), i32, i32]),
     "vcap_gpt2_generate_ragged": (i32, [C.POINTER(GPT2Desc), C.POINTER(GenParams), vp, C.POINTER(Prompts), i32, vp,
                                         vp, vp, sz, vp]),

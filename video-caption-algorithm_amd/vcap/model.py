@@ -181,6 +181,172 @@ class HipViTEncoder:
                 "vcap_vit_encode")
         return enc, pre
 
+    # ---- training: parameter gradients on the device (vcap_vit_encode_backward) -------------------------
+    _BLOCK_FIELDS = (("norm1.weight", "ln1_g"), ("norm1.bias", "ln1_b"), ("attn.qkv.weight", "qkv_w"),
+                     ("attn.qkv.bias", "qkv_b"), ("attn.proj.weight", "proj_w"), ("attn.proj.bias", "proj_b"),
+                     ("norm2.weight", "ln2_g"), ("norm2.bias", "ln2_b"), ("mlp.fc1.weight", "fc1_w"),
+                     ("mlp.fc1.bias", "fc1_b"), ("mlp.fc2.weight", "fc2_w"), ("mlp.fc2.bias", "fc2_b"))
+    _LINEARS = ("qkv", "proj", "fc1", "fc2")
+    GRAD_WORKSPACE_CAP = 12 << 30   # bytes of workspace one encode_backward chunk may take
+
+    def _check_n_tail(self, n_tail: int) -> int:
+        n_tail = int(n_tail)
+        if not 1 <= n_tail <= self.arch.depth:
+            raise ValueError(f"n_tail must be in 1..{self.arch.depth}, got {n_tail}")
+        return n_tail
+
+    def param_names(self, n_tail: int) -> List[str]:
+        """The reference's state-dict names of the parameters encode_backward(n_tail=n_tail) returns gradients
+        of: the last n_tail blocks, the final norm, encoder.proj and, with every block, the embedding."""
+        n_tail = self._check_n_tail(n_tail)
+        p = "encoder.backbone."
+        names = []
+        if n_tail == self.arch.depth:
+            names += [p + "cls_token", p + "pos_embed", p + "patch_embed.proj.weight", p + "patch_embed.proj.bias"]
+        for i in range(self.arch.depth - n_tail, self.arch.depth):
+            names += [f"{p}blocks.{i}.{k}" for k, _ in self._BLOCK_FIELDS]
+        return names + [p + "norm.weight", p + "norm.bias", "encoder.proj.weight", "encoder.proj.bias"]
+
+    def _param_shape(self, name: str) -> Tuple[int, ...]:
+        a, D = self.arch, self.arch.dim
+        tail = name.split(".", 2)[-1] if name.startswith("encoder.backbone.") else name
+        if ".blocks." in name:
+            leaf = name.split(".", 4)[-1]
+            out = {"attn.qkv": 3 * D, "attn.proj": D, "mlp.fc1": a.mlp, "mlp.fc2": D, "norm1": D, "norm2": D}[
+                leaf.rsplit(".", 1)[0]]
+            inn = a.mlp if leaf.startswith("mlp.fc2") else D
+            return (out, inn) if leaf.endswith("weight") and "norm" not in leaf else (out,)
+        return {"cls_token": (1, 1, D), "pos_embed": (1, a.tokens, D), "patch_embed.proj.weight": (D, 3, a.patch, a.patch),
+                "patch_embed.proj.bias": (D,), "norm.weight": (D,), "norm.bias": (D,),
+                "encoder.proj.weight": (self.video_dim, D), "encoder.proj.bias": (self.video_dim,)}[tail]
+
+    def _device_params(self) -> Dict[str, torch.Tensor]:
+        """name -> the device tensor the descriptor points at (the Linear weights in the operand dtype)."""
+        byptr = {t.data_ptr(): t for t in self._keep}
+        p = "encoder.backbone."
+        out = {p + "patch_embed.proj.weight": self.patch_w, p + "patch_embed.proj.bias": byptr[self.desc.patch_b],
+               p + "cls_token": byptr[self.desc.cls], p + "pos_embed": byptr[self.desc.pos],
+               p + "norm.weight": byptr[self.desc.norm_g], p + "norm.bias": byptr[self.desc.norm_b],
+               "encoder.proj.weight": self.proj_w, "encoder.proj.bias": self.proj_b}
+        for i in range(self.arch.depth):
+            for key, field in self._BLOCK_FIELDS:
+                out[f"{p}blocks.{i}.{key}"] = byptr[getattr(self.layers[i], field)]
+        return out
+
+    def enable_grad(self, sd: Dict[str, np.ndarray], n_tail: int) -> int:
+        """Upload what encode_backward needs for the last n_tail blocks beyond the inference operands: the f32
+        masters of their four Linear weights and the operand-dtype transposed copies.  Only this call pays for
+        them; returns the bytes it added."""
+        if self.dt not in (N.DT_F32, N.DT_BF16):
+            raise ValueError(f"ViT training serves precision fp32 and bf16, not {self.precision!r}")
+        n_tail = self._check_n_tail(n_tail)
+        tdt = _VIT_DTYPES[self.precision][1]
+        a = self.arch
+        self.grad_layers = (N.VitGradLayer * a.depth)()
+        self._grad_keep: Dict[str, torch.Tensor] = {}
+        added = 0
+        for i in range(a.depth - n_tail, a.depth):
+            for lin, key in zip(self._LINEARS, ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")):
+                name = f"encoder.backbone.blocks.{i}.{key}.weight"
+                m = torch.from_numpy(np.ascontiguousarray(sd[name], dtype=np.float32)).to(self.device)
+                t = m.t().contiguous().to(tdt)
+                self._grad_keep[name + "/master"], self._grad_keep[name + "/t"] = m, t
+                setattr(self.grad_layers[i], lin + "_t", t.data_ptr())
+                setattr(self.grad_layers[i], lin + "_m", m.data_ptr())
+                added += m.numel() * 4 + t.numel() * t.element_size()
+        self.grad_desc = N.VitGradDesc(dtype=self.dt, dim=a.dim, mlp=a.mlp, depth=a.depth, layers=self.grad_layers)
+        self.grad_n_tail = n_tail
+        self.grad_ws = _Workspace(self.device)
+        return added
+
+    def backward_workspace_bytes(self, B: int, T: int, n_tail: int) -> int:
+        return int(N.lib().vcap_vit_backward_workspace_bytes(C.byref(self.desc), B, T, n_tail))
+
+    def _backward_chunk(self, video: torch.Tensor, grad_out: torch.Tensor, n_tail: int):
+        B, T = video.shape[:2]
+        a, dev = self.arch, video.device
+        names = self.param_names(n_tail)
+        g = {k: torch.empty(self._param_shape(k), dtype=torch.float32, device=dev) for k in names}
+        p = "encoder.backbone."
+        pw = None
+        if n_tail == a.depth:   # the device's patch-embed gradient is [dim, kpad]
+            pw = torch.empty(a.dim, self.kpad, dtype=torch.float32, device=dev)
+        layers = (N.VitParamGradsLayer * n_tail)()
+        for j, i in enumerate(range(a.depth - n_tail, a.depth)):
+            for key, field in self._BLOCK_FIELDS:
+                setattr(layers[j], field, g[f"{p}blocks.{i}.{key}"].data_ptr())
+        pg = N.VitParamGrads(proj_w=g["encoder.proj.weight"].data_ptr(), proj_b=g["encoder.proj.bias"].data_ptr(),
+                             norm_g=g[p + "norm.weight"].data_ptr(), norm_b=g[p + "norm.bias"].data_ptr(),
+                             patch_w=N.ptr(pw), patch_b=N.ptr(g.get(p + "patch_embed.proj.bias")),
+                             cls=N.ptr(g.get(p + "cls_token")), pos=N.ptr(g.get(p + "pos_embed")), layers=layers)
+        enc = torch.empty(B, self.video_dim, dtype=torch.float32, device=dev)
+        ws = self.grad_ws.get(self.backward_workspace_bytes(B, T, n_tail))
+        N.check(N.lib().vcap_vit_encode_backward(C.byref(self.desc), C.byref(self.grad_desc), video.data_ptr(), B, T,
+                                                 n_tail, grad_out.data_ptr(), enc.data_ptr(), C.byref(pg),
+                                                 ws.data_ptr(), ws.numel(), _stream(dev)),
+                "vcap_vit_encode_backward")
+        if pw is not None:
+            g[p + "patch_embed.proj.weight"] = pw[:, :a.patch_k].reshape(a.dim, 3, a.patch, a.patch).contiguous()
+        return enc, g
+
+    def grad_chunk_clips(self, B: int, T: int, n_tail: int) -> int:
+        """The most clips (<= B) whose backward workspace fits GRAD_WORKSPACE_CAP (at least one)."""
+        c = B
+        while c > 1 and self.backward_workspace_bytes(c, T, n_tail) > self.GRAD_WORKSPACE_CAP:
+            c -= 1
+        return c
+
+    def encode_backward(self, video: torch.Tensor, grad_out: torch.Tensor, n_tail: Optional[int] = None,
+                        chunk: Optional[int] = None):
+        """video [B,T,3,H,W] f32, grad_out [B, video_dim] = d loss / d enc_out -> (enc_out with encode's bits,
+        {reference parameter name: f32 gradient}).  Clips go to the device `chunk` at a time (default: what fits
+        GRAD_WORKSPACE_CAP); the chunks' gradients are added in chunk order."""
+        if not hasattr(self, "grad_desc"):
+            raise RuntimeError("call enable_grad(sd, n_tail) before encode_backward")
+        n_tail = self._check_n_tail(self.grad_n_tail if n_tail is None else n_tail)
+        if n_tail > self.grad_n_tail:
+            raise ValueError(f"enable_grad prepared {self.grad_n_tail} block(s), n_tail = {n_tail}")
+        if video.dim() == 4:
+            video = video.unsqueeze(1)
+        a = self.arch
+        if video.dim() != 5 or tuple(video.shape[2:]) != (3, a.image, a.image):
+            raise ValueError(f"expect [B,T,3,{a.image},{a.image}], got {tuple(video.shape)}")
+        B, T = video.shape[:2]
+        if tuple(grad_out.shape) != (B, self.video_dim):
+            raise ValueError(f"grad_out must be [{B}, {self.video_dim}], got {tuple(grad_out.shape)}")
+        video = video.to(torch.float32).contiguous()
+        grad_out = grad_out.to(device=video.device, dtype=torch.float32).contiguous()
+        chunk = self.grad_chunk_clips(B, T, n_tail) if chunk is None else max(1, int(chunk))
+        encs, total = [], None
+        for b0 in range(0, B, chunk):
+            enc, g = self._backward_chunk(video[b0:b0 + chunk], grad_out[b0:b0 + chunk], n_tail)
+            encs.append(enc)
+            if total is None:
+                total = g
+            else:
+                for k in total:
+                    total[k] += g[k]
+        return (encs[0] if len(encs) == 1 else torch.cat(encs)), total
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor]) -> None:
+        """Refresh the device operands from f32 tensors (reference names) IN PLACE: the same device pointers,
+        the operand-dtype weights and, where enable_grad made them, the masters and transposed copies repacked."""
+        params = self._device_params()
+        a = self.arch
+        for name, src in state.items():
+            if name not in params:
+                raise KeyError(f"not an encoder parameter: {name}")
+            src = torch.as_tensor(src).detach().to(device=self.device, dtype=torch.float32)
+            dst = params[name]
+            if name.endswith("patch_embed.proj.weight"):
+                dst[:, :a.patch_k].copy_(src.reshape(a.dim, a.patch_k))
+            else:
+                dst.copy_(src.reshape(dst.shape))
+            keep = getattr(self, "_grad_keep", {})
+            if name + "/master" in keep:
+                keep[name + "/master"].copy_(src)
+                keep[name + "/t"].copy_(src.t())
+
 
 class HipPrefix:
     """Engine prefix normalisation (core/engine.py:44-50) + mapper (text_decoder.py:249)."""
